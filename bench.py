@@ -28,6 +28,18 @@ legs   = (N=1 only) the other BASELINE configs on one GPU -- C2 (1024 streams,
          Cauchy/parity path), C3 (one 8192-packet stream) and C5 (one stream of
          16000 x 64 KiB) -- each with the reference on the host cores beside it.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints the result line: `value`, `ms_per_step` and what
+the timed steps themselves yield (device and host times per step, the executor's
+launch time).  Everything that takes runs of its own -- cpu_baseline, legs,
+decode_ab, end_to_end, the unique-bytes step of the roofline -- runs only with
+`--full` (those keys read None without it).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed call
+returned for its last step and a digest of the bytes that step's calls produce
+(dump_stream_results, dump_stream_digests), as DIR/<name>.npy.  Payloads and the loss channel are
+seeded, so the same arguments give the same files from run to run.
+
 Multi-GPU: `bench.py --gpus N` (no WORLD_SIZE in the environment) starts N
 rank processes itself, one per GPU, from a parent that never touches the GPU;
 under torch.distributed.run the ranks come from the environment.  Barrier and
@@ -294,6 +306,55 @@ def engine_bytes(rep):
     return eng, eng["ref_op_bytes"] + eng["out_bytes"]
 
 
+RESULT_FIELDS = ("recovery_bytes payload_bytes encodes recovery_lost originals_lost recovered "
+                 "decode_calls decode_fail delivered status").split()
+
+
+def save_output(directory, name, rank, world, array):
+    """DIR/<name>.npy (DIR/<name>_rank<r>.npy when several ranks run)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ("" if world == 1 else "_rank%d" % rank) + ".npy"), array)
+
+
+def dump_stream_results(directory, rank, world, res):
+    """stream_results.npy, float64 [streams, len(RESULT_FIELDS)]: the
+    per-stream results the timed call returned for its LAST step, as its
+    caller receives them (columns: RESULT_FIELDS).  The timed steps keep no
+    event logs, so they carry no digest; the packets themselves stay in HBM
+    (dump_stream_digests)."""
+    import numpy as np
+    save_output(directory, "stream_results", rank, world,
+                np.array([[float(getattr(r, f)) for f in RESULT_FIELDS] for r in res], dtype=np.float64))
+
+
+def dump_stream_digests(directory, rank, world, args, library, device, dge):
+    """stream_digests.npy, float64 [streams, 4]: each stream's 64-bit event
+    digest as four 16-bit limbs (most significant first), with every byte of
+    every recovery packet and every recovered original hashed into it
+    (hash_data=1: the digest tests/golden pins to the reference's).
+
+    The timed steps leave their packets in HBM and hash nothing, so this is
+    one more, untimed step of the same shard through the same calls (range
+    adds, decode placement, groups and threads as timed), taken after the
+    timed steps from a session of its own; every recovered byte is also
+    checked against its payload."""
+    import numpy as np
+    cfg = S.replace(workload(rank, args.streams, args.ranges), hash_data=1)
+    sess = S.BatchSession(library, cfg, device=device)
+    try:
+        res, rep = sess.run(steps=0, warmup=1, verify=args.verify, threads=args.threads,
+                            groups=args.groups, defer=args.defer, device_ge=dge)
+    finally:
+        sess.close()
+    if args.verify and (rep.mismatches or any(r.status for r in res)):
+        raise RuntimeError("bench: verification of the dumped step failed: %d byte mismatches, status %s"
+                           % (rep.mismatches, S.summary(res)["status"]))
+    save_output(directory, "stream_digests", rank, world,
+                np.array([[float((d >> s) & 0xffff) for s in (48, 32, 16, 0)] for d in S.digests(res)],
+                         dtype=np.float64))
+
+
 def run_leg(name, library, cfg, device, threads, runs, cpu_cfg, cpu_threads, cpu_sample, defer):
     """One extra BASELINE config on one GPU: a verified warm-up, then `runs`
     timed runs ONE AT A TIME (no run overlaps another run of the same
@@ -556,11 +617,15 @@ def run_rank(rank, world, local, args, library, use_cuda):
                 "cgroup_quota_cpus": cgroup_quota(),
                 "cgroup_throttled_ms": round((thr1 - thr0) * 1e3, 2) if thr0 is not None and thr1 is not None
                 else None}
-    # one untimed step that counts the executor's compulsory bytes (every
+    if args.dump_outputs:
+        dump_stream_results(args.dump_outputs, rank, world, res)
+    # (--full) one untimed step that counts the executor's compulsory bytes (every
     # distinct symbol read once, every output written once: the roofline's
     # byte figure; counting it costs assembly time, so never in the timed run)
-    _, urep = sess.run(steps=1, warmup=0, verify=False, threads=args.threads, groups=args.groups,
-                       digest=False, defer=args.defer, device_ge=dge, unique=True)
+    urep = None
+    if args.full:
+        _, urep = sess.run(steps=1, warmup=0, verify=False, threads=args.threads, groups=args.groups,
+                           digest=False, defer=args.defer, device_ge=dge, unique=True)
     # the same steps with the other placement of the coefficient elimination
     # (host / device), timed the same way right after: reported beside
     # `value`, never as it
@@ -606,6 +671,8 @@ def run_rank(rank, world, local, args, library, use_cuda):
         cb.measure()
         side_run()
     sess.close()
+    if args.dump_outputs:
+        dump_stream_digests(args.dump_outputs, rank, world, args, library, device, dge)
 
     eng, alg_bytes = engine_bytes(rep)
     payload = rep.payload_bytes   # (all timed steps)
@@ -641,10 +708,13 @@ def run_rank(rank, world, local, args, library, use_cuda):
     traffic = traffic_capture
     if exec_traffic_step and steps:
         traffic = exec_traffic_step / (eng["exec_launches"] / steps)
-    ueng = S.engine_dict(urep)
-    unique_per_launch = ueng["exec_unique_bytes"] / max(1, ueng["exec_launches"])
     t_launch = exec_ms_per_launch / 1e3
-    unique_gbps = unique_per_launch / t_launch / 1e9 if t_launch > 0 else 0.0
+    # (the unique bytes come from the extra step of --full: None without it)
+    unique_per_launch = unique_gbps = None
+    if urep is not None:
+        ueng = S.engine_dict(urep)
+        unique_per_launch = ueng["exec_unique_bytes"] / max(1, ueng["exec_launches"])
+        unique_gbps = unique_per_launch / t_launch / 1e9 if t_launch > 0 else 0.0
     traffic_gbps = traffic / t_launch / 1e9 if traffic and t_launch > 0 else None
     # the roofline's bytes: the physical HBM traffic of this very build when
     # a PMC capture of it is committed, the compulsory bytes otherwise
@@ -725,23 +795,26 @@ def run_rank(rank, world, local, args, library, use_cuda):
         "roofline": {
             "bound": "hbm",
             "kernel": "k_exec",
-            "achieved": round(achieved, 2),
+            "achieved": round(achieved, 2) if achieved is not None else None,
             "peak": HBM_PEAK_GBPS,
             "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBPS, 4),
+            "frac": round(achieved / HBM_PEAK_GBPS, 4) if achieved is not None else None,
             "frac_basis": ("L2 <-> fabric bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE of a "
                            "separate --steps 1 capture of this same library build; MALL hits included, so "
                            "an upper bound on HBM bytes: unique_frac beside it is the compulsory floor)"
-                           if phys else "compulsory bytes per launch (no PMC capture of this build committed)"),
+                           if phys else "compulsory bytes per launch (no PMC capture of this build committed)"
+                           if urep is not None else
+                           "none: no PMC capture of this build committed, and the compulsory bytes are "
+                           "counted only with --full"),
             "traffic": round(traffic) if traffic else traffic,
             "traffic_per_capture_dispatch": traffic_capture,
             "traffic_source": traffic_src,
             "traffic_build_matches": traffic_same,
             "traffic_GBps": round(traffic_gbps, 2) if traffic_gbps else None,
             "traffic_frac": round(traffic_gbps / HBM_PEAK_GBPS, 4) if traffic_gbps else None,
-            "unique_bytes_per_launch": int(unique_per_launch),
-            "unique_GBps": round(unique_gbps, 2),
-            "unique_frac": round(unique_gbps / HBM_PEAK_GBPS, 4),
+            "unique_bytes_per_launch": int(unique_per_launch) if urep is not None else None,
+            "unique_GBps": round(unique_gbps, 2) if urep is not None else None,
+            "unique_frac": round(unique_gbps / HBM_PEAK_GBPS, 4) if urep is not None else None,
             "exec_ms_per_launch": round(exec_ms_per_launch, 4),
             "exec_launches_per_step": eng["exec_launches"] / steps,
             "achieved_alg": round(achieved_alg, 2),
@@ -824,6 +897,12 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: cpu_baseline, legs, decode_ab, "
+                         "end_to_end and the roofline's unique-bytes step (each still has its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/stream_results.npy and DIR/stream_digests.npy "
+                         "(dump_stream_results, dump_stream_digests)")
     ap.add_argument("--streams", type=int, default=STREAMS_PER_GPU)
     ap.add_argument("--cpu-streams", type=int, default=16384)
     ap.add_argument("--no-cpu", action="store_true")
@@ -858,6 +937,11 @@ def main(argv=None):
     # profiling runs over tools/libsiamese_null.so (no symbol work) only
     ap.add_argument("--no-verify", dest="verify", action="store_false", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run: set up, warm up, the timed steps, the result line
+        args.no_cpu, args.e2e, args.decode_ab, args.legs = True, False, False, False
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus, argv)

@@ -13,7 +13,7 @@ ROOT = S.ROOT
 
 
 BENCH_ARGS = ["--library", S.SIM_LIB, "--streams", "6", "--steps", "1", "--warmup", "1",
-              "--no-cpu", "--no-legs"]
+              "--full", "--no-cpu", "--no-legs"]
 
 
 def _clean_env():

@@ -11,8 +11,8 @@ byte figures are PER-DISPATCH AVERAGES (traffic_bytes_all is the sum over every
 dispatch of the capture, traffic_bytes_max the largest dispatch).  With a
 library path, "_lib_sha256" records the build the capture measured (bench.py
 reports whether the library it loads is the same build).  STEPS: the workload
-steps the captured process ran (bench.py runs --steps + --warmup + 2: the
-verified warm-up and the unique-bytes step); "_step_traffic_bytes" is then
+steps the captured process ran (bench.py --full runs --steps + --warmup + 2:
+the verified warm-up and the unique-bytes step); "_step_traffic_bytes" is then
 the traffic of all sgpu kernels per step (bench.py's physical step figure).
 """
 import hashlib
