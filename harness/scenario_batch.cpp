@@ -87,6 +87,10 @@ struct BatchReport
 namespace {
 
 constexpr int kEngineStats = 20;
+// Engine counters past BatchReport::engine[] of the last scenario_batch_run
+// (scenario_engine_more; BatchReport's layout stays as its users know it):
+// [0] sgpu_engine_stats_ex[20], chained jobs with gated k_ldpc items.
+uint64_t g_engineMore[4];
 using Clock = std::chrono::steady_clock;
 
 struct Api
@@ -1423,6 +1427,7 @@ int scenario_batch_run(void* session, StreamResult* results, const BatchOptions*
     const Api& api = *ss->api;
     Shared& sh = ss->sh;
     std::memset(report, 0, sizeof(*report));
+    std::memset(g_engineMore, 0, sizeof(g_engineMore));
     report->setup_seconds = ss->setupSeconds;
     sh.checked = sh.mismatches = 0;
     sh.e2e = opt->e2e != 0;
@@ -1494,6 +1499,13 @@ int scenario_batch_run(void* session, StreamResult* results, const BatchOptions*
         if (timed && api.arena_reserve(api.arena_bytes() / 4) != 0)
             return -2;
         uint64_t e0[kEngineStats + 1], e1[kEngineStats + 1];
+        auto chained_wide = [&]() -> uint64_t {
+            uint64_t e[kEngineStats + 1] = {};
+            if (api.engine_stats_ex)
+                api.engine_stats_ex(e, kEngineStats + 1);
+            return e[kEngineStats];
+        };
+        const uint64_t w0 = chained_wide();
         auto stats = [&](uint64_t* e) {
             for (int k = 15; k < kEngineStats; ++k)
                 e[k] = 0;
@@ -1529,12 +1541,22 @@ int scenario_batch_run(void* session, StreamResult* results, const BatchOptions*
                 report->phase_seconds[k] += phase[k];
             for (int k = 0; k <= kEngineStats; ++k)
                 report->engine[k] += e1[k] - e0[k];
+            g_engineMore[0] += chained_wide() - w0;
         }
     }
     report->checked = sh.checked;
     report->mismatches = sh.mismatches;
     print_calls();
     return rc;
+}
+
+/// The engine counters past BatchReport::engine[] over the timed steps of
+/// the last scenario_batch_run / scenario_run_batch of this process.
+extern "C" __attribute__((visibility("default")))
+void scenario_engine_more(uint64_t* out, unsigned count)
+{
+    for (unsigned k = 0; k < count && k < 4; ++k)
+        out[k] = g_engineMore[k];
 }
 
 extern "C" __attribute__((visibility("default")))

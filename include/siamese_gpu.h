@@ -137,10 +137,11 @@ SIAMESE_EXPORT SiameseResult sgpu_decode(SgpuDecoder decoder, SiameseOriginalPac
 /// what sgpu_decode would have returned, with the same outputs (an
 /// elimination that stopped short of a pivot is repeated on the host, which
 /// keeps the state the next attempt resumes from).  A square matrix of rows
-/// of one length (a block decode) is chained: the elimination of received
-/// data and the solve ride in the same submission, gated on the device
-/// elimination's outcome, so the packets this second call returns already
-/// carry their exact lengths.  While a job is pending, every other call on
+/// of one length (a block decode) is chained, rows with wide LDPC sums
+/// (windows of 512 originals or more) included: the elimination of received
+/// data (with the wide rows' LDPC picks) and the solve ride in the same
+/// submission, gated on the device elimination's outcome, so the packets
+/// this second call returns already carry their exact lengths.  While a job is pending, every other call on
 /// this decoder returns Siamese_InvalidInput.  Any other decode runs as
 /// sgpu_decode does.
 #define SGPU_DECODE_PENDING ((SiameseResult)6)
@@ -308,7 +309,8 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// launches' compulsory bytes (see sgpu_measure_unique), then the device
 /// recovery-matrix jobs (sgpu_decode_device), those of them chained into
 /// their decode's submission, and the chained ones whose matrix was singular
-/// (the host repeated the elimination); count entries at most.
+/// (the host repeated the elimination), then the chained jobs whose decode
+/// carried gated wide-row picks (k_ldpc items); count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

@@ -67,6 +67,12 @@ void be_launch_exec(const void* stream, const ExecItem* items, uint32_t count, u
 /// Wide rows' LDPC picks (ops.h LdpcItem), one workgroup per item; adds the
 /// reference's source bytes of the picks (min(len, n) each) to acct[0].
 void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct);
+/// The same for a launch that holds gated items (a chained decode's wide
+/// rows): gates has one word per item, 0 or 1 + a word of `results`; an item
+/// whose word reads zero does nothing (ops.h LdpcItem).  The caller orders
+/// the launch after the job that writes those words (be_join_ge).
+void be_launch_ldpc_gated(const LdpcItem* items, uint32_t count, uint64_t* acct, const uint32_t* gates,
+                          const uint32_t* results);
 /// The triangular solves (reference SiameseDecoder.cpp:1065-1238), one
 /// workgroup per SolveItem: every tile first solves bytes 0..3 of its rows
 /// to learn the recovered lengths, the tile-0 item writes them to `results`

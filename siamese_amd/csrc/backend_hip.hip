@@ -711,16 +711,29 @@ __device__ __forceinline__ uint32_t row_picks(uint32_t row, uint32_t N, uint32_t
 // scratch pair with one atomic per dword: the items of one row are spread
 // over the whole chip instead of running inside the codec's one workgroup
 // per tile.
+// Gated: the launch holds items of chained decodes (ops.h LdpcItem): the
+// item's gate word comes from a parallel array by a wave-uniform (scalar)
+// load, and an item whose outcome word is zero returns before it reads or
+// writes anything else.  The ungated instantiation is the kernel as it was.
 constexpr unsigned kLdpcWaves = 4;
 #ifndef SGPU_LDPC_DEPTH
 #define SGPU_LDPC_DEPTH 8
 #endif
 constexpr unsigned kLdpcDepth = SGPU_LDPC_DEPTH;   // loads in flight per lane
 
+template <bool Gated>
 __global__ __launch_bounds__(64 * kLdpcWaves) void k_ldpc(const LdpcItem* __restrict__ items,
-                                                          unsigned long long* __restrict__ acct)
+                                                          unsigned long long* __restrict__ acct,
+                                                          const uint32_t* __restrict__ gates,
+                                                          const uint32_t* results)
 {
     __shared__ uint4 part[kLdpcWaves][2][64];
+    if (Gated) {
+        // (block-uniform: every wave of the item leaves before the barrier)
+        const uint32_t gate = gates[blockIdx.x];
+        if (gate != 0 && results[gate - 1u] == 0u)
+            return;
+    }
     const LdpcItem it = items[blockIdx.x];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = uni(threadIdx.x >> 6);
@@ -4172,8 +4185,19 @@ void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct)
     if (count == 0)
         return;
     Timed t(kBeLdpc);
-    hipLaunchKernelGGL(k_ldpc, dim3(count), dim3(64 * kLdpcWaves), 0, g_stream, items,
-                       reinterpret_cast<unsigned long long*>(acct));
+    hipLaunchKernelGGL(k_ldpc<false>, dim3(count), dim3(64 * kLdpcWaves), 0, g_stream, items,
+                       reinterpret_cast<unsigned long long*>(acct), (const uint32_t*)nullptr,
+                       (const uint32_t*)nullptr);
+}
+
+void be_launch_ldpc_gated(const LdpcItem* items, uint32_t count, uint64_t* acct, const uint32_t* gates,
+                          const uint32_t* results)
+{
+    if (count == 0)
+        return;
+    Timed t(kBeLdpc);
+    hipLaunchKernelGGL(k_ldpc<true>, dim3(count), dim3(64 * kLdpcWaves), 0, g_stream, items,
+                       reinterpret_cast<unsigned long long*>(acct), gates, results);
 }
 
 void be_launch_ge(const GeDesc* descs, const uint8_t* in, uint32_t count, uint32_t* results, SolveRow* rows,

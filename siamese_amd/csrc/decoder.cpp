@@ -1421,7 +1421,12 @@ bool DecoderCore::submit_device_ge(bool chained)
 // host's sums go back to their state before it, chain_sums_restore), and the
 // job writes the solve's coefficients and row order itself.  The host side of
 // BackSubstitution waits for finish_chained.  Siamese rows of wide LDPC sums
-// are not chained (their k_ldpc items are not gated).
+// (ldpcCount >= kLdpcSplitMin) are chained too: their k_ldpc items take the
+// gate of the OP_ROWS op that reads them (Program::gate_end, ops.h LdpcItem).
+// When the elimination of received data or the solve cannot be queued, the
+// job owns no solve and is cancelled at assembly (ops.h GeDesc): it reports outcome
+// 0, so nothing gated runs, and finish_chained disables the decoder with its
+// sums as they were.
 bool DecoderCore::submit_chained()
 {
     const unsigned columns = region_.lostCount;
@@ -1432,7 +1437,7 @@ bool DecoderCore::submit_chained()
     const RecPacket* r = region_.first;
     const unsigned bytes = r->bytes;
     for (unsigned i = 0; i < rows; ++i, r = r->next)
-        if ((r->meta.sumCount > kCauchyThreshold && r->meta.ldpcCount >= kLdpcSplitMin) || r->bytes != bytes)
+        if (r->bytes != bytes)
             return false;
     if (!submit_device_ge(true))
         return false;
@@ -1457,7 +1462,8 @@ bool DecoderCore::submit_chained()
     chainElimFailed_ = !eliminate_original_data();
     deferAccount_ = false;
     deferRelease_ = false;
-    prog_.gate_end();
+    if (prog_.gate_end())
+        eng_->shard().stats.geChainedWide++;
     const uint64_t c2 = kDecodeClocks ? __rdtsc() : 0;
     chainSlot_ = ~0u;
     chainBytes_ = bytes;
@@ -1528,6 +1534,14 @@ SiameseResult DecoderCore::finish_chained(SiameseOriginalPacket** packetsOut, un
         chain_sums_commit();
         return Siamese_Disabled;
     }
+    if (chainElimFailed_) {
+        // the job was cancelled (no solve was queued for it): nothing gated
+        // ran, and the decoder is lost as the host path would lose it
+        drop_solve();
+        chain_sums_restore();
+        disabled_ = true;
+        return Siamese_Disabled;
+    }
     if (!ok) {
         // a singular matrix: nothing gated ran (the elimination of received
         // data, its sum updates, the solve).  The sums go back to their state
@@ -1548,11 +1562,6 @@ SiameseResult DecoderCore::finish_chained(SiameseOriginalPacket** packetsOut, un
     eng_->account(((uint64_t)o[2] << 32) | o[1]);
     eng_->account(deferredBytes_);
     eng_->account((uint64_t)o[4] * chainBytes_, 0, true);
-    if (chainElimFailed_) {
-        drop_solve();
-        disabled_ = true;
-        return Siamese_Disabled;
-    }
     const uint8_t* piv = reinterpret_cast<const uint8_t*>(o + ge_out_pivots(geRows_));
     scratchRec_.resize(columns);
     scratchLen_.resize(columns);

@@ -50,6 +50,7 @@ void EngineStats::add(const EngineStats& o)
     geJobs += o.geJobs;
     geChained += o.geChained;
     geRetried += o.geRetried;
+    geChainedWide += o.geChainedWide;
 }
 
 namespace {
@@ -669,15 +670,20 @@ void Program::gate_begin(uint32_t word)
     b_->gateWord = word;
 }
 
-void Program::gate_end()
+uint32_t Program::gate_end()
 {
     if (!b_ || !b_->gateOpen)
-        return;
+        return 0;
     b_->rows_close();
     b_->gateOpen = false;
     ProgramBody::Segment& s = b_->segs[b_->gateSeg];
-    if (b_->gateSeg + 1 == b_->nsegs && s.ops.size() > b_->gateOp)
+    uint32_t wide = 0;
+    if (b_->gateSeg + 1 == b_->nsegs && s.ops.size() > b_->gateOp) {
         s.gates.push_back(ProgramBody::Segment::Gate{b_->gateOp, (uint32_t)s.ops.size(), b_->gateWord});
+        for (const ProgramBody::Segment::Wide& x : s.wide)
+            wide += x.op >= b_->gateOp;
+    }
+    return wide;
 }
 
 uint8_t* Program::ge_job(unsigned rows, unsigned cols, unsigned pickLen, uint32_t* resultWord, bool chained)
@@ -691,7 +697,7 @@ uint8_t* Program::ge_job(unsigned rows, unsigned cols, unsigned pickLen, uint32_
     g.pickLen = pickLen;
     g.result = b_->resultWords;
     g.chained = chained;
-    g.solve = 0;
+    g.solve = ~0u;   // (none until a gated solve_commit matches it)
     b_->resultWords += ge_result_words(rows, cols, chained);
     g.in.resize(ge_input_bytes(rows, cols, pickLen));
     *resultWord = g.result;
@@ -1409,6 +1415,8 @@ struct Batch
     bool geChained = false;                 // a job writes into the upload (kGeChained)
     size_t oCopy = 0;                      // the download copy list (BeCopy records)
     uint64_t wideBase = 0;                 // this submission's k_ldpc scratch: bytes into the ring
+    bool wideGated = false;                // k_ldpc items of gated ops: the launches take the gate
+    size_t oWideGate = 0;                  // ... array (one word per item, ops.h LdpcItem)
     bool wideZero = false;                 // the ring wrapped: zero it before the first exec launch
     uint32_t resultWords = 0;
     std::vector<const Shard::Download*> dls;
@@ -2070,6 +2078,9 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
                     continue;
                 segs[i].wideBase = (uint32_t)nWide;
                 segs[i].wideOff = wideBytes;
+                // (a gate range holds whole ops, so a gated segment with wide
+                // rows may hold gated wide rows: the launches then take gates)
+                bt.wideGated = bt.wideGated || !s.gates.empty();
                 nWide += s.wideItems;
                 wideBytes += s.wideBytes;
             }
@@ -2138,6 +2149,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     {
         const ProgramBody::PendingGe* g;
         size_t inOff;
+        bool cancelled;   // a chained job without its solve: a 1 x 1 zero matrix instead (ops.h GeDesc)
     };
     std::vector<GeDesc> gdescs;
     std::vector<GeRef> grefs;
@@ -2154,16 +2166,26 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
                 d.rows = ge.rows;
                 d.cols = ge.cols;
                 d.pickLen = ge.pickLen;
-                if (ge.chained && ge.solve < p->nsolves) {
+                bool cancelled = false;
+                if (ge.chained) {
+                    // (the job owns the solve a gated solve_commit matched to
+                    // it; without one it is cancelled: a zero matrix in its
+                    // place reports outcome 0 and writes no solve, ops.h GeDesc)
                     d.flags = kGeChained;
-                    d.solveRow = p->solves[ge.solve].asmRow;
-                    d.solveCoef = p->solves[ge.solve].asmCoef;
+                    if (ge.solve < p->nsolves) {
+                        d.solveRow = p->solves[ge.solve].asmRow;
+                        d.solveCoef = p->solves[ge.solve].asmCoef;
+                    } else {
+                        cancelled = true;
+                        d.rows = d.cols = 1;
+                        d.pickLen = 0;
+                    }
                     bt.geChained = true;
                 }
-                bt.geMaxRows = std::max<uint32_t>(bt.geMaxRows, ge.rows);
-                bt.geMaxCols = std::max<uint32_t>(bt.geMaxCols, ge.cols);
+                bt.geMaxRows = std::max<uint32_t>(bt.geMaxRows, d.rows);
+                bt.geMaxCols = std::max<uint32_t>(bt.geMaxCols, d.cols);
                 gdescs.push_back(d);
-                grefs.push_back(GeRef{&ge, geInBytes});
+                grefs.push_back(GeRef{&ge, geInBytes, cancelled});
                 geInBytes = align16(geInBytes + ge.in.size());
             }
         }
@@ -2225,6 +2247,9 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     off = align16(off + sitems.size() * sizeof(SolveItem));
     bt.oWide = off;
     off = align16(off + nWide * sizeof(LdpcItem));
+    bt.oWideGate = off;
+    if (bt.wideGated)
+        off = align16(off + nWide * sizeof(uint32_t));
     // the download copy list (the counters and results, then every range)
     size_t nDownloads = 0;
     for (const Shard::Queues& q : bt.queues)
@@ -2305,18 +2330,21 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
                 uint8_t* w = up + bt.oStream + (size_t)r.wordBase * 16;
                 size_t wi = 0;                                      // next wide row
                 LdpcItem* wItem = (LdpcItem*)(up + bt.oWide) + r.wideBase;
+                uint32_t* wGate = bt.wideGated ? (uint32_t*)(up + bt.oWideGate) + r.wideBase : nullptr;
                 uint64_t wOff = bt.wideBase + r.wideOff;
                 size_t gi = 0;   // next gated range
                 for (uint32_t oi = 0; oi < (uint32_t)s.ops.size(); ++oi) {
                     const GfOp& op = s.ops[oi];
                     std::memcpy(w, &op, sizeof(GfOp));
+                    uint32_t opGate = 0;   // the op's gate, absolute (its wide rows' k_ldpc items take it too)
                     if (op.kind != OP_LITERAL) {
                         // termBegin on the device: the op's gate, 1 + a result
                         // word (ops.h GeDesc), or 0
                         while (gi < s.gates.size() && s.gates[gi].opEnd <= oi)
                             ++gi;
                         const bool gated = gi < s.gates.size() && s.gates[gi].opBegin <= oi;
-                        reinterpret_cast<GfOp*>(w)->termBegin = gated ? 1u + s.gates[gi].word + r.resultBase : 0u;
+                        opGate = gated ? 1u + s.gates[gi].word + r.resultBase : 0u;
+                        reinterpret_cast<GfOp*>(w)->termBegin = opGate;
                     }
                     w += sizeof(GfOp);
                     if (op.kind == OP_ROWS || op.kind == OP_COPIES || op.kind == OP_LINCOMBS) {
@@ -2350,6 +2378,8 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
                                     it.tileBase = t;
                                     it.pair0 = p0;
                                     it.pair1 = std::min(pairs, p0 + ppi);
+                                    if (wGate)
+                                        *wGate++ = opGate;
                                 }
                         }
                         w += bytes;
@@ -2368,8 +2398,19 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
                                           exec_tiles(t, std::min(r.tilesPerItem, tiles - t))};
             }
         } else if (t.kind == 3) {
-            for (size_t i = t.a; i < t.b; ++i)
-                std::memcpy(up + bt.oGeIn + grefs[i].inOff, grefs[i].g->in.data(), grefs[i].g->in.size());
+            for (size_t i = t.a; i < t.b; ++i) {
+                uint8_t* in = up + bt.oGeIn + grefs[i].inOff;
+                if (grefs[i].cancelled) {
+                    // one parity row over no column, one column (the job's
+                    // own input is at least as long: ge_input_bytes)
+                    std::memset(in, 0, ge_input_bytes(1, 1, 0));
+                    GeRow* r = reinterpret_cast<GeRow*>(in);
+                    r->kind = GE_PARITY;
+                    r->colCount = 1;
+                    continue;
+                }
+                std::memcpy(in, grefs[i].g->in.data(), grefs[i].g->in.size());
+            }
         } else if (t.kind == 2) {
             for (size_t i = t.a; i < t.b; ++i) {
                 const SolveRef& r = srefs[i];
@@ -2522,10 +2563,17 @@ void Engine::launch_batch(Batch& bt)
     size_t wideDone = 0;
     for (size_t k = 0; k < bt.phases.size() && bt.phases[k].kind == Phase::EXEC; ++k)
         wideDone = bt.phases[k].wideBegin + bt.phases[k].wideCount;
+    // (gated items: the launches take the gate array, and come after the
+    // matrix jobs that write the outcome words)
+    const uint32_t* wideGates = bt.wideGated ? (const uint32_t*)(bt.upBase + bt.oWideGate) : nullptr;
     if (wideDone) {
-        if (ingested)
+        if (ingested || wideGates)
             be_join_ge();   // (its items and the elements they read came with the side stream)
-        be_launch_ldpc((const LdpcItem*)(bt.upBase + bt.oWide), (uint32_t)wideDone, acctDev + 3);
+        if (wideGates)
+            be_launch_ldpc_gated((const LdpcItem*)(bt.upBase + bt.oWide), (uint32_t)wideDone, acctDev + 3, wideGates,
+                                 resultsDev);
+        else
+            be_launch_ldpc((const LdpcItem*)(bt.upBase + bt.oWide), (uint32_t)wideDone, acctDev + 3);
     }
     // The codec stream joins the matrix jobs before the first executor launch
     // (they run beside k_ingest): joined only before the decoders' phases,
@@ -2535,9 +2583,14 @@ void Engine::launch_batch(Batch& bt)
     for (const Phase& ph : bt.phases) {
         be_join_ge();   // (no-op once joined)
         if (ph.kind == Phase::EXEC) {
-            if (ph.wideCount && ph.wideBegin >= wideDone)
-                be_launch_ldpc((const LdpcItem*)(bt.upBase + bt.oWide) + ph.wideBegin, (uint32_t)ph.wideCount,
-                               acctDev + 3);
+            if (ph.wideCount && ph.wideBegin >= wideDone) {
+                const LdpcItem* items = (const LdpcItem*)(bt.upBase + bt.oWide) + ph.wideBegin;
+                if (wideGates)
+                    be_launch_ldpc_gated(items, (uint32_t)ph.wideCount, acctDev + 3, wideGates + ph.wideBegin,
+                                         resultsDev);
+                else
+                    be_launch_ldpc(items, (uint32_t)ph.wideCount, acctDev + 3);
+            }
             be_launch_exec(bt.upBase + bt.oStream, (const ExecItem*)(bt.upBase + bt.oItems) + ph.itemBegin,
                            (uint32_t)ph.itemCount, acctDev, resultsDev, ph.maxRows);
             st.execLaunches++;

@@ -295,7 +295,7 @@ struct ProgramBody
         uint32_t pickLen = 0;
         uint32_t result = 0;
         bool chained = false;   // kGeChained: feeds solves[solve] of the same body
-        uint32_t solve = 0;
+        uint32_t solve = ~0u;   // (~0u: no gated solve_commit matched it: cancelled at assembly)
         std::vector<uint8_t> in;
     };
 
@@ -442,8 +442,11 @@ public:
     /// Gate every op queued from now until gate_end() on result word `word`:
     /// they run only if it is non-zero (a chained matrix job's outcome, ops.h
     /// GeDesc word 3).  No solve and no literal may be queued in between.
+    /// The k_ldpc items of wide rows queued in between take the same gate
+    /// (made absolute at assembly like the ops'); gate_end returns how many
+    /// wide rows the range holds.
     void gate_begin(uint32_t word);
-    void gate_end();
+    uint32_t gate_end();
 
     /// Run `fn(results)` once the flush holding this program's work completes.
     /// Callbacks of one flush run in registration order on one thread, but
@@ -541,6 +544,7 @@ struct EngineStats
     // device recovery-matrix jobs (sgpu_decode_device): all, chained into
     // their decode's submission, chained ones that found a singular matrix
     uint64_t geJobs = 0, geChained = 0, geRetried = 0;
+    uint64_t geChainedWide = 0;   // chained jobs whose decode carried gated k_ldpc items (wide rows)
 
     void add(const EngineStats& o);
 };

@@ -167,6 +167,14 @@ constexpr unsigned kRowWords = sizeof(RowItem) / 16;
 /// window index of two entries appended to the batch's window that name L0
 /// and L1, and adds them to acc0 and acc1 like two draws.  The same bytes
 /// meet in a different order, which GF(2^8) addition (XOR) does not see.
+///
+/// Gated items (a chained decode's wide rows, GeDesc kGeChained): LdpcItem has
+/// no spare field, so a launch that holds gated items takes a parallel array
+/// of one gate word per item, 0 or 1 + a result word as GfOp.termBegin: the
+/// item does nothing (writes nothing, counts nothing) when that word is zero,
+/// its scratch pair stays zero, and the kRowWide row that would read it lies
+/// in the same gated OP_ROWS op.  Launches without gated items take no array
+/// and run the ungated instantiation of the kernel.
 struct LdpcItem
 {
     uint64_t win;        // device address of the batch's window entry 0 (WinEntry[])
@@ -413,6 +421,10 @@ inline unsigned solve_tile_bytes(uint32_t m)
 /// coefficients in pivot order (coef + solveCoef, cols x cols) and permutes
 /// the solve's rows (rows + solveRow) into pivot order, each keeping its head
 /// slot (SolveRow.headIndex).
+/// A chained job whose solve the host could not queue (Program::solve_commit
+/// never matched it) owns none: assembly replaces it by a 1 x 1 job of one
+/// parity row without columns (a zero matrix), which reports outcome [3] = 0
+/// and touches no solve, so every item gated on it is skipped.
 /// Row kinds: Siamese (dense over [0, jEnd) from the row's opcodes, then
 /// 2*ceil(ldpcN/16) PCG picks over [pickOff, pickOff + ldpcN)), Cauchy
 /// (1/((rbase) ^ ccol) over [0, jEnd)) and parity (1 over [0, jEnd)).
