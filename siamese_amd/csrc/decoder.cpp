@@ -29,11 +29,41 @@ inline unsigned first_clear(uint64_t bits, unsigned from)
     return inv ? (unsigned)__builtin_ctzll(inv) : 64;
 }
 
+// SGPU_WALK_COUNT (a measuring build): nodes visited by list_insert's search
+// and by check_recovery_possible's walk, summed over all decoders and printed
+// at exit when SIAMESE_AMD_WALK_COUNTS is set; with SGPU_WALK_FULL as well,
+// neither shortcut is taken (the counts before them).  SGPU_WALK_CHECK (the test
+// double's build): the search from the tail and the walk from the head are
+// repeated beside their shortcuts and must agree, or the process aborts.
+#if defined(SGPU_WALK_CHECK) && !defined(SGPU_WALK_COUNT)
+#define SGPU_WALK_COUNT
+#endif
+#ifdef SGPU_WALK_COUNT
+struct WalkCounts
+{
+    std::atomic<uint64_t> decoders{0}, inserts{0}, insertHops{0}, checks{0}, checkVisits{0}, shortcuts{0};
+    ~WalkCounts()
+    {
+        if (!std::getenv("SIAMESE_AMD_WALK_COUNTS"))
+            return;
+        std::fprintf(stderr, "walk counts: decoders %llu inserts %llu insert_hops %llu checks %llu "
+                     "check_visits %llu shortcuts %llu\n",
+                     (unsigned long long)decoders.load(), (unsigned long long)inserts.load(),
+                     (unsigned long long)insertHops.load(), (unsigned long long)checks.load(),
+                     (unsigned long long)checkVisits.load(), (unsigned long long)shortcuts.load());
+    }
+} g_walk;
+#define SGPU_WALK_VISIT(field) ((void)g_walk.field.fetch_add(1, std::memory_order_relaxed))
+#else
+#define SGPU_WALK_VISIT(field) ((void)0)
+#endif
+
 } // namespace
 
 DecoderCore::DecoderCore(Engine* eng, bool hostMirror)
     : eng_(eng), prog_(eng, 1), mirror_(hostMirror)
 {
+    SGPU_WALK_VISIT(decoders);
     adopt_spare();
     if (!res_)
         res_ = std::make_shared<Resolver>();
@@ -183,6 +213,8 @@ DecoderCore::~DecoderCore()
         free_packet(r);
         r = n;
     }
+    head_ = tail_ = runFirst_ = nullptr;
+    walkMemo_.valid = false;
     // one pass over each subwindow: release the buffers slots own and leave
     // every slot fresh, so the pool's recycle (DecSubwindowRecycle) need not
     // walk them again (a decoder's teardown is memory-bound on these slots)
@@ -226,6 +258,7 @@ bool DecoderCore::mark_got(unsigned column)
     DecSubwindow* sw = subwindows_[element / kSubwindow].get();
     sw->gotCount++;
     sw->got |= 1ULL << (element % kSubwindow);
+    ++windowGen_;
     return element == nextExpected_;
 }
 
@@ -281,6 +314,7 @@ void DecoderCore::iterate_next_expected(unsigned start)
     if (nextExpected_ >= count_)
         return;
     nextExpected_ = find_next_lost(start);
+    ++windowGen_;
 }
 
 bool DecoderCore::grow_window(unsigned end)
@@ -289,9 +323,12 @@ bool DecoderCore::grow_window(unsigned end)
     while (subwindows_.size() < needed) {
         subwindows_.emplace_back(ObjPool<DecSubwindow>::get());
         subwindows_.back()->clean = false;
+        ++windowGen_;
     }
-    if (end > count_)
+    if (end > count_) {
         count_ = end;
+        ++windowGen_;
+    }
     return true;
 }
 
@@ -324,6 +361,7 @@ SiameseResult DecoderCore::accept_original(unsigned element, unsigned column, un
 
     sw->gotCount++;
     sw->got |= 1ULL << bit;
+    ++windowGen_;
 
     if (element == nextExpected_) {
         iterate_next_expected(element + 1);
@@ -731,6 +769,7 @@ void DecoderCore::remove_elements()
     count_ -= removed;
     columnStart_ = element_to_column(removed);
     nextExpected_ -= removed;
+    ++windowGen_;   // (elements renumber: the list's ranges too)
 
     for (RecPacket* p = head_; p; p = p->next) {
         p->elementEnd -= removed;
@@ -782,8 +821,30 @@ void DecoderCore::list_insert(RecPacket* r, bool outOfOrder)
     RecPacket* next = nullptr;
     const unsigned rs = r->meta.columnStart;
     const unsigned re = r->elementEnd;
+    // A packet with the tail's key (a block's recovery packets all have it)
+    // breaks at no node of the tail's run of that key: the search below
+    // would step over the whole run, so it starts in front of it.
+#ifndef SGPU_WALK_FULL
+    const bool tailKey = tail_ && re == tail_->elementEnd && rs == tail_->meta.columnStart;
+#else
+    const bool tailKey = false;
+#endif
+    if (tailKey) {
+        if (!runFirst_) {
+            // (dropped, or never known: found again once per run)
+            runFirst_ = tail_;
+            while (runFirst_->prev && runFirst_->prev->elementEnd == re &&
+                   runFirst_->prev->meta.columnStart == rs) {
+                runFirst_ = runFirst_->prev;
+                SGPU_WALK_VISIT(insertHops);
+            }
+        }
+        next = runFirst_;
+        prev = runFirst_->prev;
+    }
     // Keep both edges of the recovery ranges monotone (SiameseDecoder.h:40-50)
     for (; prev; next = prev, prev = prev->prev) {
+        SGPU_WALK_VISIT(insertHops);
         const unsigned pe = prev->elementEnd;
         if (re >= pe) {
             if (re > pe)
@@ -792,6 +853,21 @@ void DecoderCore::list_insert(RecPacket* r, bool outOfOrder)
                 break;
         }
     }
+    SGPU_WALK_VISIT(inserts);
+#ifdef SGPU_WALK_CHECK
+    {
+        // the reference's search from the tail ends at the same place
+        RecPacket* p = tail_;
+        RecPacket* n = nullptr;
+        for (; p; n = p, p = p->prev) {
+            const unsigned pe = p->elementEnd;
+            if (re > pe || (re == pe && column_delta_negative(column_sub(rs, p->meta.columnStart))))
+                break;
+        }
+        if (p != prev || n != next)
+            walk_check_failed("list_insert: position differs from the search from the tail");
+    }
+#endif
     r->next = next;
     r->prev = prev;
     if (prev)
@@ -802,6 +878,15 @@ void DecoderCore::list_insert(RecPacket* r, bool outOfOrder)
         next->prev = r;
     else
         tail_ = r;
+    // the tail's run: a new tail starts one (with the old tail's key the
+    // search never stops behind the tail); a packet of the run's key put
+    // right in front of it joins it; any other lands in front of the run
+    // or further up (the search decides alike at every node of the run)
+    if (!next)
+        runFirst_ = r;
+    else if (tailKey && next == runFirst_)
+        runFirst_ = r;
+    ++listGen_;
     if (!prev || next)
         region_reset(); // a smaller solution may now exist
     ++listCount_;
@@ -823,10 +908,14 @@ void DecoderCore::list_delete_before(unsigned element)
         // DESIGN.md "Deviations").  Drop such a region instead.
         if (r == region_.first || r == region_.last)
             regionStale = true;
+        if (r == runFirst_)
+            runFirst_ = nullptr;   // (the run shares its end: all of it goes)
         free_packet(r);
         ++deleted;
         r = n;
     }
+    if (deleted)
+        ++listGen_;
     if (regionStale)
         region_reset();
     head_ = r;
@@ -890,6 +979,7 @@ SiameseResult DecoderCore::add_recovery_common(const RowMeta& m, int footer, uns
             return Siamese_Success;
         }
         columnStart_ = m.columnStart;
+        ++windowGen_;
         grow_window(m.sumCount);
         elementEnd = m.sumCount;
         elementStart = elementEnd - m.ldpcCount;
@@ -1062,10 +1152,21 @@ bool DecoderCore::check_recovery_possible()
         return false;
     RecPacket* r;
     unsigned nextCheck, recCount, lost;
-    if (!region_.last) {
+    SGPU_WALK_VISIT(checks);
+    const bool fromHead = !region_.last;
+    if (fromHead) {
         r = head_;
         if (!r)
             return false;
+        if (walk_shortcut()) {
+#ifdef SGPU_WALK_CHECK
+            walk_check();
+#endif
+            if (region_.lostCount > kMaxLossRecovery)
+                return false;
+            return region_.recoveryCount >= region_.lostCount;
+        }
+        SGPU_WALK_VISIT(checkVisits);
         region_.first = r;
         region_.elementStart = r->elementStart;
         recCount = 1;
@@ -1081,7 +1182,10 @@ bool DecoderCore::check_recovery_possible()
         r = region_.last;
         nextCheck = region_.nextCheckStart;
     }
+    bool walked = fromHead;
     while ((recCount < lost || region_.solveFailed) && r->next) {
+        SGPU_WALK_VISIT(checkVisits);
+        walked = true;
         r = r->next;
         ++recCount;
         unsigned end = r->elementEnd;
@@ -1096,10 +1200,100 @@ bool DecoderCore::check_recovery_possible()
     region_.recoveryCount = recCount;
     region_.lostCount = lost;
     region_.nextCheckStart = nextCheck;
+    if (walked) {
+        // Remember a walk from the head that reached the tail short of
+        // packets with the head's count all the way (the ranges after the
+        // head's added nothing lost): see walk_shortcut.  Any other walk
+        // wrote lostCount values the memo does not describe.
+        walkMemo_.valid = fromHead && !r->next && recCount < lost && head_->lostCount == lost;
+        if (walkMemo_.valid) {
+            walkMemo_.head = head_;
+            walkMemo_.tail = r;
+            walkMemo_.elementStart = head_->elementStart;
+            walkMemo_.elementEnd = head_->elementEnd;
+            walkMemo_.windowGen = windowGen_;
+            walkMemo_.listGen = listGen_;
+            walkMemo_.listCount = listCount_;
+            walkMemo_.lost = lost;
+            walkMemo_.nextCheckStart = nextCheck;
+            walkMemo_.recoveryCount = recCount;
+        }
+    }
     if (lost > kMaxLossRecovery)
         return false;
     return recCount >= lost && !region_.solveFailed;
 }
+
+// check_recovery_possible from the head, when the only change since the
+// remembered walk is one packet put in front of that walk's head with the
+// head's element range (a block's next recovery packet).  The walk would give
+// the new head the old head's count (range_lost over the same range of the
+// same window), find nothing lost between the two (the old head's range ends
+// where the new one's does), and then repeat the remembered walk with one
+// packet more: the remembered walk went on at each of its n nodes but the
+// last because i < lost, and n < lost at the last, so this one, at i + 1 <=
+// n < lost, goes on to the tail too; every count it would write is `lost`,
+// which the nodes hold.  Its outcome is set here; anything else: false, and
+// the walk runs.
+bool DecoderCore::walk_shortcut()
+{
+    const RecPacket* h = head_;
+#ifdef SGPU_WALK_FULL
+    walkMemo_.valid = false;
+#endif
+    if (!walkMemo_.valid || windowGen_ != walkMemo_.windowGen || listGen_ != walkMemo_.listGen + 1 ||
+        h->next != walkMemo_.head || tail_ != walkMemo_.tail || listCount_ != walkMemo_.listCount + 1 ||
+        h->elementStart != walkMemo_.elementStart || h->elementEnd != walkMemo_.elementEnd)
+        return false;
+    head_->lostCount = walkMemo_.lost;
+    region_.first = head_;
+    region_.elementStart = head_->elementStart;
+    region_.last = tail_;
+    region_.recoveryCount = walkMemo_.recoveryCount + 1;
+    region_.lostCount = walkMemo_.lost;
+    region_.nextCheckStart = walkMemo_.nextCheckStart;
+    region_.solveFailed = false;
+    // (still short of packets: the next insert in front finds this walk)
+    walkMemo_.valid = region_.recoveryCount < region_.lostCount;
+    walkMemo_.head = head_;
+    walkMemo_.listGen = listGen_;
+    walkMemo_.listCount = listCount_;
+    walkMemo_.recoveryCount = region_.recoveryCount;
+    SGPU_WALK_VISIT(shortcuts);
+    return true;
+}
+
+#ifdef SGPU_WALK_CHECK
+void DecoderCore::walk_check_failed(const char* what)
+{
+    std::fprintf(stderr, "SGPU_WALK_CHECK: %s\n", what);
+    std::abort();
+}
+
+// The walk from the head, into locals: every field walk_shortcut set and
+// every lostCount must be what it leaves.
+void DecoderCore::walk_check()
+{
+    RecPacket* r = head_;
+    unsigned recCount = 1, nextCheck = r->elementEnd;
+    unsigned lost = range_lost(r->elementStart, nextCheck);
+    bool same = r->lostCount == lost;
+    while (recCount < lost && r->next) {
+        r = r->next;
+        ++recCount;
+        unsigned end = r->elementEnd;
+        if (end < nextCheck)
+            end = nextCheck;
+        lost += range_lost(nextCheck, end);
+        nextCheck = end;
+        same = same && r->lostCount == lost;
+    }
+    if (!same || region_.first != head_ || region_.elementStart != head_->elementStart || region_.last != r ||
+        region_.recoveryCount != recCount || region_.lostCount != lost || region_.nextCheckStart != nextCheck ||
+        region_.solveFailed)
+        walk_check_failed("check_recovery_possible: the shortcut differs from the walk");
+}
+#endif
 
 SiameseResult DecoderCore::is_ready()
 {
@@ -1160,6 +1354,7 @@ SiameseResult DecoderCore::decode_loop(SiameseOriginalPacket** packetsOut, unsig
             end = nextCheck;
         lost += range_lost(nextCheck, end);
         r->lostCount = lost;
+        walkMemo_.valid = false;   // (counts check_recovery_possible did not write)
         nextCheck = end;
     }
     region_.last = r;

@@ -366,6 +366,14 @@ private:
     unsigned listCount_ = 0;
     RowMeta lastMeta_;
     unsigned lastBytes_ = 0;
+    // list_insert: the node nearest the head of the run of consecutive
+    // nodes at the tail that share the tail's key (elementEnd,
+    // meta.columnStart); null: unknown (found again on the next insert of
+    // the tail's key).  A packet with the tail's key steps over the whole
+    // run, so its search starts in front of it.
+    RecPacket* runFirst_ = nullptr;
+    uint64_t listGen_ = 0;     // moves on every insert into and delete from the list
+    uint64_t windowGen_ = 0;   // moves when range_lost may answer differently or elements renumber
 
     // checked region
     struct
@@ -377,6 +385,27 @@ private:
         unsigned recoveryCount = 0, lostCount = 0;
         bool solveFailed = false;
     } region_;
+    // check_recovery_possible's last walk from the head, when it reached the
+    // tail short of packets (it survives region_reset).  While the window
+    // and the list stay as they were, the nodes' lostCount are what that
+    // walk wrote, and the walk after one insert in front of its head with
+    // the head's element range is known without repeating it (see
+    // check_recovery_possible).
+    struct
+    {
+        bool valid = false;
+        RecPacket* head = nullptr;   // the walk's first node ...
+        RecPacket* tail = nullptr;   // ... and its last, the list's tail
+        unsigned elementStart = 0, elementEnd = 0;   // the head's range
+        uint64_t windowGen = 0, listGen = 0;
+        unsigned listCount = 0;
+        unsigned lost = 0, nextCheckStart = 0, recoveryCount = 0;   // its outcome
+    } walkMemo_;
+    bool walk_shortcut();
+#ifdef SGPU_WALK_CHECK
+    void walk_check();
+    [[noreturn]] static void walk_check_failed(const char* what);
+#endif
 
     // recovery matrix
     struct RowInfo
