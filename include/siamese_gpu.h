@@ -155,6 +155,51 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_get(SgpuDecoder decoder, SiameseOrigin
 /// returned.  Returns the result of the get that stopped (Success if none).
 SIAMESE_EXPORT SiameseResult sgpu_decoder_get_range(SgpuDecoder decoder, unsigned firstPacketNum, unsigned count,
                                                     SiameseOriginalPacket* packets, unsigned* gotOut);
+/// Queue the delivery of packets firstPacketNum .. firstPacketNum+count-1 into
+/// caller-owned device memory: packet k's payload (no length prefix) at
+/// deviceDst + k*stride, bytes [len, stride) of that row zero, and its length
+/// in deviceLens[k] (uint32, device memory).  Never waits for the GPU: rows and
+/// lengths are in place when the submission that carries this call completes
+/// (sgpu_flush / sgpu_wait / sgpu_query == 1).  The counterpart of
+/// sgpu_decoder_add_original_range on the way out.
+///
+/// Present packets (received or recovered, including one whose solve is
+/// queued in this same submission and whose length is still pending): row
+/// and length are written, results[k] = Siamese_Success.
+/// Absent packets: results[k] = Siamese_NeedMoreData, deviceLens[k] = 0 is
+/// written and the row is left untouched, so a stream may be delivered into
+/// one buffer again and again as it fills in.  *queuedOut = the number of
+/// present packets; the call returns Siamese_Success even when some are
+/// absent.
+/// deviceLens[k] == 0 always means "row k holds no packet" (a packet is never
+/// 0 bytes).  A packet that is present but does not fit, which only the
+/// device can see for a packet still being solved -- a corrupt recovered
+/// length prefix, a length past the symbol's capacity, a length above stride
+/// -- gets a zeroed row and deviceLens[k] = 0; the decoder itself reports a
+/// corrupt prefix as it always does (Siamese_Disabled once the submission has
+/// completed).
+///
+/// Siamese_InvalidInput, with nothing queued: a null decoder; null deviceDst
+/// or deviceLens with count > 0; deviceDst not 16-byte aligned; stride zero,
+/// not a multiple of 16 or above 4 GiB; deviceLens not 4-byte aligned;
+/// firstPacketNum > SIAMESE_PACKET_NUM_MAX; a packet of the range whose exact
+/// length is already known and exceeds stride; a decoder with a device matrix
+/// job pending (sgpu_decode_device).  A dead decoder returns
+/// Siamese_Disabled.  count == 0 returns Siamese_Success with *queuedOut = 0.
+///
+/// The caller guarantees that nothing else reads or writes the rows or the
+/// lengths from this call until that submission completes; two deliveries
+/// into overlapping rows in one submission are undefined.  The arena's
+/// lifetime rule is unchanged and the caller need not think about it here:
+/// the delivery reads the symbols after every other device launch of its
+/// submission, and a symbol that a later call of the same submission drops
+/// (the window sliding on, the decoder freed) is recycled only after the
+/// submission has completed.  Delivery of an encoder's recovery packets and a
+/// list (non-range) form are not offered.
+SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_range(SgpuDecoder decoder, unsigned firstPacketNum, unsigned count,
+                                                        void* deviceDst, size_t stride, unsigned* deviceLens,
+                                                        SiameseResult* results /* host, optional */,
+                                                        unsigned* queuedOut);
 /// sgpu_decode without waiting (see "Deferred outputs" above): the recovered
 /// packets are written to out[0, *countOut), PacketNum at once, Data and
 /// DataBytes at once or when the solve's submission completes.  capacity must
@@ -294,8 +339,8 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// Device milliseconds per kernel class since the last sgpu_timing reset,
 /// while timing is enabled: [0] k_ingest, [1] k_exec, [2] k_ldpc, [3] the
 /// solve kernels (k_solve_pre + k_solve_tr + k_solve_main on launches of
-/// >= 16 solves, k_solve_main alone below that), [4] k_ge (sgpu_decode_device);
-/// count entries at most.
+/// >= 16 solves, k_solve_main alone below that), [4] k_ge (sgpu_decode_device),
+/// [5] k_deliver (sgpu_decoder_deliver_range); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -310,7 +355,10 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// recovery-matrix jobs (sgpu_decode_device), those of them chained into
 /// their decode's submission, and the chained ones whose matrix was singular
 /// (the host repeated the elimination), then the chained jobs whose decode
-/// carried gated wide-row picks (k_ldpc items); count entries at most.
+/// carried gated wide-row picks (k_ldpc items), then [21] the delivery items
+/// queued (sgpu_decoder_deliver_range: one per packet of each range, absent
+/// ones included, counted when their submission is laid out); count entries
+/// at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

@@ -109,6 +109,19 @@ void be_side_upload_ingest(const BeCopy* rest, const IngestDesc* descs, uint32_t
                            const uint32_t* blocks, uint32_t nblocks);
 void be_join_ge();
 
+/// Packets into caller-owned rows (ops.h DeliverItem), one wave per (item,
+/// kIngestChunkBytes chunk of its row).  maxStride: the largest row among the
+/// items in bytes, saturated to 32 bits (sizes the grid).  The caller queues
+/// it after every launch that writes the symbols (and after be_join_ge()).
+/// A weak reference: a program that links the control plane with a backend
+/// that has no delivery (a test double built from fewer files) still links.
+/// There the address is null, be_has_deliver() says so, and
+/// sgpu_decoder_deliver_range refuses with Siamese_Disabled and a message
+/// instead of queueing work no kernel would run.  The HIP backend and the
+/// CPU test double of the suite both define it.
+void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStride) __attribute__((weak));
+inline bool be_has_deliver() { return be_launch_deliver != nullptr; }
+
 /// Block until all queued work has finished.  Returns false on a device fault.
 bool be_sync();
 
@@ -146,7 +159,7 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-enum BeKernel { kBeIngest, kBeExec, kBeLdpc, kBeSolve, kBeGe, kBeKernelKinds };
+enum BeKernel { kBeIngest, kBeExec, kBeLdpc, kBeSolve, kBeGe, kBeDeliver, kBeKernelKinds };
 void be_timing_enable(bool on);
 /// Device milliseconds of one kernel class since the last reset
 /// (be_timing_exec_ms is kBeExec's).

@@ -17,6 +17,8 @@
 //                  sweeps: small launches, flagged solves)
 //   k_solve_prefix the length pass alone (sweeps-only launches)
 //   k_ge           a decode's recovery matrix and its elimination (opt-in)
+//   k_deliver      decoded packets into caller-owned rows at a fixed stride,
+//                  lengths beside them (k_ingest backwards, opt-in)
 //
 // GF(256) multiply by a wave-uniform constant uses three v_perm_b32 byte
 // lookups per dword (bits 0-2, 3-5, 6-7 of each byte) and one v_bitop3_b32
@@ -3710,6 +3712,89 @@ __global__ __launch_bounds__(kGeThreads) void k_ge(const GeDesc* __restrict__ de
 }
 
 // ---------------------------------------------------------------------------
+// Delivery (k_deliver, ops.h DeliverItem)
+//
+// k_ingest run backwards: one wave per (item, 8 KiB chunk of its row), lane L
+// of each 1 KiB tile writes row bytes [16L, 16L+16) with one 16-byte store.
+// The wave reads the symbol's first aligned word, parses the length prefix
+// (header h = 1..4 bytes, length L) and checks it against the symbol's
+// readable bytes and the row; everything derived from it is wave-uniform.
+// The payload starts at src + h, so a lane's 16 output bytes straddle the
+// aligned source words at src + p and src + p + 16: both are loaded
+// (coalesced) and recombined with v_alignbyte_b32, the shift chosen by a
+// uniform branch on h.  A word is loaded only if the row needs a payload byte
+// from it (p < L, and p + 16 < h + L for the second), which keeps every read
+// inside the aligned words that hold a byte of [src, src + cap), since
+// h + L <= cap.  Bytes at and past L are masked to zero and the zero fill
+// runs to the row's end; rows and positions are 64-bit (rows of up to 4 GiB).
+// Two tiles' loads are in flight before their stores.  No LDS, no atomics.
+
+__global__ __launch_bounds__(64 * kDeliverWaves) void k_deliver(const DeliverItem* __restrict__ items,
+                                                                uint32_t count)
+{
+    const uint32_t ii = __builtin_amdgcn_readfirstlane(blockIdx.x * kDeliverWaves + (threadIdx.x >> 6));
+    if (ii >= count)
+        return;
+    const uint32_t lane = threadIdx.x & 63;
+    const DeliverItem it = items[ii];
+    const uint64_t stride = (uint64_t)it.stride16 << 4;
+    uint32_t h = 0, L = 0;
+    if (it.src != 0 && it.cap != 0) {   // (uniform)
+        const uint32_t avail = it.cap < 4 ? it.cap : 4;
+        const uint32_t w = __builtin_amdgcn_readfirstlane(ld16(it.src).x) & byte_mask((int)avail);
+        uint32_t len = 0;
+        const int hh = parse_prefix(w, avail, &len);
+        if (hh >= 1 && len >= 1 && (uint32_t)hh + len <= it.cap && len <= stride) {
+            h = (uint32_t)hh;
+            L = len;
+        }
+    }
+    if (blockIdx.y == 0 && lane == 0)
+        *reinterpret_cast<GMEM uint32_t*>(it.lenOut) = L;
+    if (it.src == 0)   // an absent packet: its row stays as it is
+        return;
+    const uint32_t end = h + L;   // symbol bytes in use (0: a zeroed row)
+    const uint64_t step = (uint64_t)gridDim.y * kIngestChunkBytes;
+    for (uint64_t c0 = (uint64_t)blockIdx.y * kIngestChunkBytes; c0 < stride; c0 += step) {
+        const uint64_t c1 = c0 + kIngestChunkBytes < stride ? c0 + kIngestChunkBytes : stride;
+        for (uint64_t t = c0; t < c1; t += 2 * kTileBytes) {
+            uint4 out[2];
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                const uint4 lo = p < L ? ld16(it.src + p) : make_uint4(0, 0, 0, 0);
+                const uint4 hi = p + 16 < end ? ld16(it.src + p + 16) : make_uint4(0, 0, 0, 0);
+                const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                switch (h) {   // wave-uniform
+                case 1:
+                    out[u] = make_uint4(pick(w, 0, 1, 0), pick(w, 0, 1, 1), pick(w, 0, 1, 2), pick(w, 0, 1, 3));
+                    break;
+                case 2:
+                    out[u] = make_uint4(pick(w, 0, 2, 0), pick(w, 0, 2, 1), pick(w, 0, 2, 2), pick(w, 0, 2, 3));
+                    break;
+                case 3:
+                    out[u] = make_uint4(pick(w, 0, 3, 0), pick(w, 0, 3, 1), pick(w, 0, 3, 2), pick(w, 0, 3, 3));
+                    break;
+                default:   // h = 4 (or a zeroed row: nothing was loaded)
+                    out[u] = make_uint4(w[1], w[2], w[3], w[4]);
+                    break;
+                }
+            }
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                if (p >= stride)
+                    continue;
+                uint4 v = out[u];
+                if (p + 16 > L)
+                    v = mask16(v, p < L ? (int)(L - (uint32_t)p) : 0);
+                st16(it.dst + p, v);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 
 namespace {
@@ -4162,6 +4247,18 @@ void be_launch_ingest(const IngestDesc* descs, uint32_t count, uint32_t maxBytes
     if (grid == 0)
         return;
     hipLaunchKernelGGL(k_ingest, dim3(grid, chunks), dim3(64 * kIngestWaves), 0, g_stream, descs, count, blocks);
+}
+
+void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStride)
+{
+    if (count == 0)
+        return;
+    Timed t(kBeDeliver);
+    // (a wave walks the chunks of a row the grid is too short for)
+    const uint32_t chunks =
+        std::min(kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxStride + kIngestChunkBytes - 1) / kIngestChunkBytes)));
+    hipLaunchKernelGGL(k_deliver, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
+                       g_stream, items, count);
 }
 
 void be_launch_exec(const void* stream, const ExecItem* items, uint32_t count, uint64_t* acct,

@@ -282,6 +282,30 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_get_range(SgpuDecoder decoder, unsigne
     return BD(decoder)->core.get_range(firstPacketNum, count, packets, gotOut);
 }
 
+SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_range(SgpuDecoder decoder, unsigned firstPacketNum, unsigned count,
+                                                        void* deviceDst, size_t stride, unsigned* deviceLens,
+                                                        SiameseResult* results, unsigned* queuedOut)
+{
+    if (queuedOut)
+        *queuedOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, lens = (uint64_t)(uintptr_t)deviceLens;
+    if (!decoder || BD(decoder)->core.ge_pending() || ((!deviceDst || !deviceLens) && count) || (dst & 15u) ||
+        stride == 0 || (stride & 15u) || (uint64_t)stride > (1ull << 32) || (lens & 3u) ||
+        firstPacketNum > SIAMESE_PACKET_NUM_MAX)
+        return Siamese_InvalidInput;
+    if (!be_has_deliver()) {
+        // (a missing kernel is an error, never a quiet no-op: backend.h)
+        std::fprintf(stderr, "siamese_amd: this backend has no delivery kernel (be_launch_deliver)\n");
+        return Siamese_Disabled;
+    }
+    unsigned queued = 0;
+    const SiameseResult r =
+        BD(decoder)->core.deliver_range(firstPacketNum, count, dst, (uint64_t)stride, lens, results, &queued);
+    if (queuedOut)
+        *queuedOut = queued;
+    return r;
+}
+
 SIAMESE_EXPORT SiameseResult sgpu_decode_deferred(SgpuDecoder decoder, SiameseOriginalPacket* out,
                                                   unsigned capacity, unsigned* countOut)
 {
@@ -578,12 +602,13 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[21] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[22] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
-                            s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide};
-    for (unsigned k = 0; k < count && k < 21; ++k)
+                            s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide,
+                            s.delivers};
+    for (unsigned k = 0; k < count && k < 22; ++k)
         out[k] = v[k];
 }
 

@@ -2734,6 +2734,39 @@ SiameseResult DecoderCore::get_range(unsigned firstNum, unsigned count, SiameseO
     return Siamese_Success;
 }
 
+SiameseResult DecoderCore::deliver_range(unsigned firstNum, unsigned count, uint64_t dst, uint64_t stride,
+                                         uint64_t lens, SiameseResult* results, unsigned* queued)
+{
+    *queued = 0;
+    settle();
+    if (dead())
+        return Siamese_Disabled;
+    // the window walked as get_range walks it; nothing is queued when a packet
+    // whose exact length is known cannot fit its row
+    const unsigned e0 = column_to_element(firstNum);
+    unsigned e = e0;
+    for (unsigned k = 0; k < count; ++k, e = (e + 1) % kColumnPeriod)
+        if (e < count_) {
+            const DecSlot& s = slot(e);
+            if (s.bytes != 0 && !s.pending && s.bytes - s.header > stride)
+                return Siamese_InvalidInput;
+        }
+    e = e0;
+    for (unsigned k = 0; k < count; ++k, e = (e + 1) % kColumnPeriod) {
+        const DecSlot* s = e < count_ ? &slot(e) : nullptr;
+        const bool present = s && s->bytes != 0;
+        // (a pending slot's bytes are its row's finalBytes: the device reads
+        // the recovered prefix and checks it against them and the stride)
+        prog_.deliver(present ? s->buf.addr() : 0, present ? s->bytes : 0, dst + (uint64_t)k * stride,
+                      lens + (uint64_t)k * 4, stride);
+        if (results)
+            results[k] = present ? Siamese_Success : Siamese_NeedMoreData;
+        if (present)
+            ++*queued;
+    }
+    return Siamese_Success;
+}
+
 SiameseResult DecoderCore::decode_deferred(SiameseOriginalPacket* out, unsigned capacity, unsigned* countOut)
 {
     settle();

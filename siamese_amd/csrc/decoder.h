@@ -130,6 +130,16 @@ public:
     /// into out[0..count) until one is not Success; *got = packets returned.
     /// Returns the result of the get that stopped (Success if none did).
     SiameseResult get_range(unsigned firstNum, unsigned count, SiameseOriginalPacket* out, unsigned* got);
+    /// sgpu_decoder_deliver_range: queue the delivery of packets firstNum,
+    /// firstNum + 1, ... into the caller's device rows dst + k * stride, their
+    /// lengths into the uint32 words at lens + 4 k (Program::deliver, one item
+    /// per packet; an absent packet's item writes only a zero length).  Never
+    /// waits: a recovered packet whose length is still pending is delivered
+    /// by the device from its prefix.  results[k] (optional) = Success /
+    /// NeedMoreData, *queued = packets present.  InvalidInput, with nothing
+    /// queued, when a packet's known length exceeds the stride.
+    SiameseResult deliver_range(unsigned firstNum, unsigned count, uint64_t dst, uint64_t stride, uint64_t lens,
+                                SiameseResult* results, unsigned* queued);
     /// Host-memory recovery packet (drop-in API).
     SiameseResult add_recovery(const SiameseRecoveryPacket& packet);
     /// Device-resident recovery packet (batch API).

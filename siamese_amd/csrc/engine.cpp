@@ -51,6 +51,7 @@ void EngineStats::add(const EngineStats& o)
     geChained += o.geChained;
     geRetried += o.geRetried;
     geChainedWide += o.geChainedWide;
+    delivers += o.delivers;
 }
 
 namespace {
@@ -113,6 +114,7 @@ void ProgramBody::clear()
     rb.rows.clear();
     copies.clear();
     lcb.clear();
+    ndeliver = 0;   // (the items' vector keeps its elements: not touched here)
     gateOpen = false;
 }
 
@@ -869,6 +871,20 @@ void Program::copy(uint64_t dst, uint64_t src, uint32_t len)
         g.maxExtent = len;
 }
 
+void Program::deliver(uint64_t src, uint32_t cap, uint64_t dst, uint64_t lenOut, uint64_t stride)
+{
+    touch();
+    DeliverItem it;
+    it.src = src;
+    it.dst = dst;
+    it.lenOut = lenOut;
+    it.cap = cap;
+    it.stride16 = (uint32_t)(stride >> 4);
+    if (b_->ndeliver == b_->delivers.size())
+        b_->delivers.emplace_back();
+    b_->delivers[b_->ndeliver++] = it;
+}
+
 // ---------------------------------------------------------------------------
 // Shard queues
 
@@ -1413,6 +1429,8 @@ struct Batch
     bool allGated = false;                  // every solve of the submission is a chained job's
     uint32_t geMaxRows = 0, geMaxCols = 0;  // ... their largest matrix (k_ge's LDS)
     bool geChained = false;                 // a job writes into the upload (kGeChained)
+    size_t oDeliver = 0, nDeliver = 0;     // delivery items of every body (ops.h DeliverItem)
+    uint32_t maxDeliverStride = 0;         // ... their longest row in bytes, saturated (k_deliver's grid)
     size_t oCopy = 0;                      // the download copy list (BeCopy records)
     uint64_t wideBase = 0;                 // this submission's k_ldpc scratch: bytes into the ring
     bool wideGated = false;                // k_ldpc items of gated ops: the launches take the gate
@@ -2154,9 +2172,11 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     std::vector<GeDesc> gdescs;
     std::vector<GeRef> grefs;
     size_t geInBytes = 0;
+    size_t nDeliver = 0;   // delivery items of every body
     for (int g = 0; g < 2; ++g)
         for (size_t pi = 0; pi < bt.bodies[g].size(); ++pi) {
             const ProgramBody* p = bt.bodies[g][pi];
+            nDeliver += p->ndeliver;   // (beside nges: no line of the body this pass does not read anyway)
             for (size_t k = 0; k < p->nges; ++k) {
                 const ProgramBody::PendingGe& ge = p->ges[k];
                 GeDesc d;
@@ -2190,6 +2210,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
             }
         }
     bt.nGe = gdescs.size();
+    bt.nDeliver = nDeliver;
 
     constexpr size_t kIngestChunk = SGPU_INGEST_CHUNK;
     size_t nIngest = 0, stageBytes = 0, nIngBlocks = 0;
@@ -2250,6 +2271,10 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     bt.oWideGate = off;
     if (bt.wideGated)
         off = align16(off + nWide * sizeof(uint32_t));
+    // the delivery items of every body, in body order (one launch runs them
+    // all after the last phase: launch_batch)
+    bt.oDeliver = off;
+    off = align16(off + nDeliver * sizeof(DeliverItem));
     // the download copy list (the counters and results, then every range)
     size_t nDownloads = 0;
     for (const Shard::Queues& q : bt.queues)
@@ -2444,6 +2469,20 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     }
     if (!gdescs.empty())
         std::memcpy(up + bt.oGeD, gdescs.data(), gdescs.size() * sizeof(GeDesc));
+    if (nDeliver) {
+        DeliverItem* di = (DeliverItem*)(up + bt.oDeliver);
+        uint32_t max16 = 0;
+        for (int g = 0; g < 2; ++g)
+            for (const ProgramBody* p : bt.bodies[g]) {
+                if (p->ndeliver == 0)
+                    continue;
+                std::memcpy(di, p->delivers.data(), p->ndeliver * sizeof(DeliverItem));
+                for (uint32_t k = 0; k < p->ndeliver; ++k)
+                    max16 = std::max(max16, di[k].stride16);
+                di += p->ndeliver;
+            }
+        bt.maxDeliverStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
+    }
 
     // download area: the byte counters (kAcctBytes), the solve results, then
     // each requested range
@@ -2474,7 +2513,8 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     }
 
     st.flushes = 1;
-    st.launches = phases.size() + (nIngest ? 1 : 0) + (gdescs.empty() ? 0 : 1);
+    st.launches = phases.size() + (nIngest ? 1 : 0) + (gdescs.empty() ? 0 : 1) + (nDeliver ? 1 : 0);
+    st.delivers = nDeliver;
     st.ops = nOps;
     st.terms = nTerms;
     st.solves = sdescs.size();
@@ -2602,10 +2642,23 @@ void Engine::launch_batch(Batch& bt)
                             (uint32_t)ph.solveCount);
         }
     }
+    be_join_ge();
+    // The submission's deliveries, after its last executor / solve launch:
+    // the symbols are final, a recovered packet's length prefix included, and
+    // every buffer a call of this submission released is still untouched
+    // (released buffers return to the arena in reclaim_batch, after the fence).
+    if (bt.nDeliver) {
+        // (sgpu_decoder_deliver_range queues nothing on a backend without the
+        // kernel, backend.h: items that got here anyway fail the engine)
+        if (be_has_deliver())
+            be_launch_deliver((const DeliverItem*)(bt.upBase + bt.oDeliver), (uint32_t)bt.nDeliver,
+                              bt.maxDeliverStride);
+        else
+            failed_.store(true, std::memory_order_relaxed);
+    }
     // the counters and solve results, then the downloads, in one call (one
     // kernel when small; its range list was laid out with the upload: a
     // drop-in submission carries a range per application call)
-    be_join_ge();
     be_copy_list(bt.copies.data(), xs.downHostDev ? bt.upBase + bt.oCopy : nullptr, (unsigned)bt.copies.size(),
                  false);
     bt.fence = be_fence();

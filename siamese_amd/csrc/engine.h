@@ -306,7 +306,10 @@ struct ProgramBody
     std::vector<PendingSolve> solves;   // solve k follows segment k (nsolves in use)
     size_t nsolves = 0;
     std::vector<PendingGe> ges;         // independent of the segments (nges in use)
-    size_t nges = 0;
+    uint32_t nges = 0;
+    // items in `delivers` (below), beside the counts every submission reads:
+    // a body without deliveries costs detach and assembly no cache line more
+    uint32_t ndeliver = 0;
     std::vector<Completion> callbacks;
     // objects the callbacks use, kept alive until they have run (so a
     // callback captures a raw pointer and fits std::function's inline
@@ -341,6 +344,10 @@ struct ProgramBody
         }
     } lcb;
     std::vector<GfTerm> lcScratch;
+    /// Packets to hand to the caller's device memory (ops.h DeliverItem):
+    /// independent of the segments, run by the submission's one k_deliver
+    /// launch after all of them.  ndeliver in use (capacity is kept).
+    std::vector<DeliverItem> delivers;
     void lc_seal();                     // seals the open OP_LINCOMBS batch
     /// Move the segment's last op (an OP_LINCOMB) into the open batch, or
     /// seal the batch first when they are not independent.
@@ -350,7 +357,7 @@ struct ProgramBody
 
     bool empty() const
     {
-        return nges == 0 &&
+        return nges == 0 && ndeliver == 0 &&
                (nsegs == 0 ||
                 (nsegs == 1 && segs[0].ops.empty() && copies.empty() && lcb.items.empty() && !rb.open));
     }
@@ -503,6 +510,14 @@ public:
     /// the batch touches.
     void copy(uint64_t dst, uint64_t src, uint32_t len);
 
+    /// Queue a delivery item (ops.h DeliverItem): the symbol at src (0: an
+    /// absent packet), of which `cap` bytes may be read, into the caller's row
+    /// dst[0, stride) with its length at lenOut.  All of a submission's items
+    /// run in one launch after its last executor / solve launch, whatever the
+    /// order of the calls: the item reads the symbol as the submission leaves
+    /// it.  A program whose only work is delivery still makes a submission.
+    void deliver(uint64_t src, uint32_t cap, uint64_t dst, uint64_t lenOut, uint64_t stride);
+
     bool empty() const { return !b_ || b_->empty(); }
 
 private:
@@ -545,6 +560,7 @@ struct EngineStats
     // their decode's submission, chained ones that found a singular matrix
     uint64_t geJobs = 0, geChained = 0, geRetried = 0;
     uint64_t geChainedWide = 0;   // chained jobs whose decode carried gated k_ldpc items (wide rows)
+    uint64_t delivers = 0;        // delivery items queued (sgpu_decoder_deliver_range)
 
     void add(const EngineStats& o);
 };
@@ -560,7 +576,12 @@ public:
     bool ready() const { return ready_; }
 
     DevBuf alloc(uint32_t bytes);
-    void release(DevBuf& b);               // recycled after the next flush completes
+    /// Recycled after the next flush completes: the buffer joins the calling
+    /// thread's queue, which that submission takes whole and returns to the
+    /// depot only when it has completed (reclaim_batch).  Every launch of the
+    /// submission, its delivery launch (the last one) included, therefore
+    /// still reads a symbol that a later call of the same submission dropped.
+    void release(DevBuf& b);
     /// Slot `bit` of the slab for a symbol of `need` bytes (the slab is
     /// taken on first use), or a null buffer when it cannot hold it (taken
     /// slot, too large, slabs off); *failed on an arena failure.

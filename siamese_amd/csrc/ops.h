@@ -387,6 +387,34 @@ constexpr uint32_t kIngestRunMax = 64;
 /// k_ingest work per workgroup: one symbol per wave.
 constexpr uint32_t kIngestWaves = 4;
 
+/// Delivery of one decoder packet into caller-owned device memory (k_deliver,
+/// sgpu_decoder_deliver_range): k_ingest run backwards.  The symbol at src
+/// (16-byte aligned, its 1-4 byte length prefix at byte 0) is read on the
+/// device: header h and length L from the prefix (reference
+/// SiameseSerializers.h:598-640), valid when L >= 1, h + L <= cap and
+/// L <= stride.  Then dst[0, L) = src[h, h + L), dst[L, stride) = 0 and
+/// *lenOut = L; an invalid packet counts as L = 0 (a zeroed row).  src = 0: an
+/// absent packet, only *lenOut = 0 is written.  Only aligned 16-byte words
+/// holding a byte of [src, src + cap) are read, nothing outside
+/// [dst, dst + stride) and the length word is written.  The launch runs after
+/// every other launch of its submission, so the prefix of a packet whose solve
+/// rides in the same submission is already in place.
+struct DeliverItem
+{
+    uint64_t src;        // the symbol (0: absent)
+    uint64_t dst;        // the row, 16-byte aligned
+    uint64_t lenOut;     // uint32 length word, 4-byte aligned
+    uint32_t cap;        // bytes of the symbol that may be read: header + length
+                         // of a received packet, finalBytes of a pending row
+    uint32_t stride16;   // the row's bytes / 16 (1 .. 2^28: rows of up to 4 GiB)
+};
+static_assert(sizeof(DeliverItem) == 32, "DeliverItem layout");
+/// k_deliver work per workgroup: one item per wave, as k_ingest; a wave takes
+/// the kIngestChunkBytes chunks blockIdx.y, blockIdx.y + gridDim.y, ... of its
+/// row, and a launch has at most kDeliverMaxChunks chunk rows in its grid.
+constexpr uint32_t kDeliverWaves = 4;
+constexpr uint32_t kDeliverMaxChunks = 4096;
+
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)
 /// Solves with more rows than this stage 256-byte tiles (16 lanes x 16 bytes
