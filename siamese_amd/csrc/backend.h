@@ -1,7 +1,8 @@
 // backend.h -- the only interface between the host control plane and the
 // device.  libsiamese_amd.so implements it with HIP on gfx950
 // (backend_hip.hip).  A host simulation of the same contract exists ONLY for
-// the CPU test suite (tests/hostsim/), never in the shipped library.
+// the CPU test suite (tools/backend_hostsim.cpp, linked into
+// tests/hostsim/libsiamese_hostsim.so), never in the shipped library.
 #pragma once
 
 #include "ops.h"
@@ -48,12 +49,19 @@ void be_copy_pinned(const BeCopy* ranges, unsigned count, bool toDevice);
 /// ranges too large for a kernel, fall back to be_copy_pinned.
 void be_copy_list(const BeCopy* ranges, const void* devList, unsigned count, bool toDevice);
 
-/// One wave per (descriptor, kIngestChunkBytes chunk): maxBytes is the
-/// largest hdrLen + bytes among the descriptors (sizes the grid).
-/// blocks: the k_ingest block table (nblocks entries, descriptor << 4 |
-/// 4-symbol group of its run), or null for runs of one (one per wave).
-void be_launch_ingest(const IngestDesc* descs, uint32_t count, uint32_t maxBytes, const uint32_t* blocks = nullptr,
-                      uint32_t nblocks = 0);
+/// One k_ingest launch.  One wave per (descriptor, kIngestChunkBytes chunk):
+/// maxBytes is the largest hdrLen + bytes among the descriptors (sizes the
+/// grid).  blocks: the k_ingest block table (nblocks entries, descriptor << 4
+/// | 4-symbol group of its run), or null for runs of one (one per wave).
+struct BeIngest
+{
+    const IngestDesc* descs;
+    uint32_t count;
+    uint32_t maxBytes;
+    const uint32_t* blocks = nullptr;
+    uint32_t nblocks = 0;
+};
+void be_launch_ingest(const BeIngest& ingest);
 /// `stream`: the instruction words of every segment (see ExecItem).
 /// `acct`: device counter the executor adds the reference's source bytes of
 /// the terms it expands itself (sum updates, LDPC picks) to (ops.h).
@@ -66,13 +74,12 @@ void be_launch_exec(const void* stream, const ExecItem* items, uint32_t count, u
                     const uint32_t* results, uint32_t maxWindow);
 /// Wide rows' LDPC picks (ops.h LdpcItem), one workgroup per item; adds the
 /// reference's source bytes of the picks (min(len, n) each) to acct[0].
-void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct);
-/// The same for a launch that holds gated items (a chained decode's wide
-/// rows): gates has one word per item, 0 or 1 + a word of `results`; an item
-/// whose word reads zero does nothing (ops.h LdpcItem).  The caller orders
-/// the launch after the job that writes those words (be_join_ge).
-void be_launch_ldpc_gated(const LdpcItem* items, uint32_t count, uint64_t* acct, const uint32_t* gates,
-                          const uint32_t* results);
+/// gates (or null: every item runs): one word per item, 0 or 1 + a word of
+/// `results`; an item whose word reads zero does nothing (a chained decode's
+/// wide rows, ops.h LdpcItem).  The caller orders a gated launch after the job
+/// that writes those words (be_join_ge).
+void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct, const uint32_t* gates = nullptr,
+                    const uint32_t* results = nullptr);
 /// The triangular solves (reference SiameseDecoder.cpp:1065-1238), one
 /// workgroup per SolveItem: every tile first solves bytes 0..3 of its rows
 /// to learn the recovered lengths, the tile-0 item writes them to `results`
@@ -87,40 +94,52 @@ void be_launch_solve(const SolveDesc* solves, const SolveRow* rows, const uint8_
 /// Device recovery-matrix generation + elimination (ops.h GeDesc): one job
 /// per desc, its input at in + desc.in, its output in results + desc.result;
 /// a kGeChained job that succeeds also writes its solve's coefficients
-/// (coef + solveCoef) and permutes its SolveRows (rows + solveRow).  Reads
-/// nothing any other launch of the flush writes.  It may run beside the
-/// launches queued after it until be_join_ge(), after which every launch
-/// (and the results' download) sees its outputs.  maxRows / maxCols: the
-/// largest job of the launch (sizes its LDS).  head (or null): a pinned H2D
-/// copy that brings the jobs' inputs, rows and coefficients into place, run
-/// ahead of them on their own stream (beside the codec stream's copies); it
-/// must not overlap anything the codec stream writes or copies.
-/// rowsIn (or null: rows): where a chained job reads its solve rows before it
-/// writes them to `rows` in pivot order; with descs, in and rowsIn in mapped
-/// pinned memory and no head, the jobs need no copy at all.
-void be_launch_ge(const GeDesc* descs, const uint8_t* in, uint32_t count, uint32_t* results, SolveRow* rows,
-                  uint8_t* coef, uint32_t maxRows, uint32_t maxCols, const BeCopy* head, bool side = true,
-                  const SolveRow* rowsIn = nullptr);
-/// The other arrangement: with side = false the jobs (and their head copy)
-/// run in order on the codec stream, and this puts the rest of the upload
-/// (`rest`, or null) and k_ingest (be_launch_ingest's arguments) on the side
-/// stream beside them; be_join_ge joins it.
-void be_side_upload_ingest(const BeCopy* rest, const IngestDesc* descs, uint32_t count, uint32_t maxBytes,
-                           const uint32_t* blocks, uint32_t nblocks);
+/// (coef + solveCoef) and its SolveRows (rows + solveRow) in pivot order,
+/// read from rowsIn + solveRow.  Reads nothing any other launch of the flush
+/// writes.  maxRows / maxCols: the largest job of the launch (sizes its LDS).
+struct BeGe
+{
+    const GeDesc* descs;
+    const uint8_t* in;
+    uint32_t count;
+    uint32_t* results;
+    const SolveRow* rowsIn;   // `rows` itself, or the same rows in the mapped upload
+    SolveRow* rows;
+    uint8_t* coef;
+    uint32_t maxRows, maxCols;
+};
+/// Where the jobs of a submission run.  Both placements fork the side stream
+/// from the codec stream first; be_join_ge() puts the codec stream behind the
+/// side stream again, after which every launch (and the results' download)
+/// sees the jobs' outputs.
+enum class GePlace
+{
+    /// In line on the codec stream, after `head` when it has bytes (`head`
+    /// belongs to this placement alone; kSideStream ignores it): a pinned
+    /// H2D copy that brings the jobs' descriptors, inputs, rows and
+    /// coefficients into place.  No bytes: descs, in and rowsIn are mapped
+    /// pinned memory (be_host_device_ptr) and the jobs need no copy at all.
+    /// The caller puts the rest of the upload and k_ingest beside the jobs
+    /// with be_side_upload_ingest.
+    kCodecStream,
+    /// On the side stream, beside whatever the codec stream queues until
+    /// be_join_ge() (a submission whose upload is not copied: nothing to put
+    /// beside the jobs but the codec stream's own next launches).
+    kSideStream,
+};
+void be_launch_ge(const BeGe& ge, GePlace place, const BeCopy& head = BeCopy{0, 0, 0});
+/// After be_launch_ge(GePlace::kCodecStream): the rest of the upload (when
+/// it has bytes) and k_ingest on the side stream, beside the jobs.
+void be_side_upload_ingest(const BeCopy& rest, const BeIngest& ingest);
 void be_join_ge();
 
 /// Packets into caller-owned rows (ops.h DeliverItem), one wave per (item,
-/// kIngestChunkBytes chunk of its row).  maxStride: the largest row among the
-/// items in bytes, saturated to 32 bits (sizes the grid).  The caller queues
-/// it after every launch that writes the symbols (and after be_join_ge()).
-/// A weak reference: a program that links the control plane with a backend
-/// that has no delivery (a test double built from fewer files) still links.
-/// There the address is null, be_has_deliver() says so, and
-/// sgpu_decoder_deliver_range refuses with Siamese_Disabled and a message
-/// instead of queueing work no kernel would run.  The HIP backend and the
-/// CPU test double of the suite both define it.
-void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStride) __attribute__((weak));
-inline bool be_has_deliver() { return be_launch_deliver != nullptr; }
+/// kIngestChunkBytes chunk of its row): each row gets its packet's payload
+/// and a zero tail, and its length word (zero for an absent packet or one
+/// whose prefix does not fit).  maxStride: the largest row among the items
+/// in bytes, saturated to 32 bits (sizes the grid).  The caller queues it
+/// after every launch that writes the symbols (and after be_join_ge()).
+void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStride);
 
 /// Block until all queued work has finished.  Returns false on a device fault.
 bool be_sync();
@@ -161,11 +180,9 @@ bool be_mark_sync(void* mark);
 /// Kernel classes of the per-launch device timing.
 enum BeKernel { kBeIngest, kBeExec, kBeLdpc, kBeSolve, kBeGe, kBeDeliver, kBeKernelKinds };
 void be_timing_enable(bool on);
-/// Device milliseconds of one kernel class since the last reset
-/// (be_timing_exec_ms is kBeExec's).
+/// Device milliseconds of one kernel class since the last reset.
 double be_timing_kernel_ms(BeKernel kind);
 void be_timing_reset();
-double be_timing_exec_ms();
 double be_timing_total_ms();
 
 } // namespace sgpu

@@ -3802,8 +3802,9 @@ namespace {
 hipStream_t g_stream = nullptr;
 hipStream_t g_stageStream = nullptr;    // application H2D staging (be_stage_h2d)
 hipStream_t g_gatherStream = nullptr;   // gathers of completed results (be_gather)
-// device recovery-matrix jobs (k_ge) beside the submission's first launches
-// (be_launch_ge / be_join_ge)
+// the side stream of a submission with device recovery-matrix jobs: the rest
+// of the upload and k_ingest beside k_ge, or k_ge beside the codec stream
+// (be_launch_ge / be_side_upload_ingest / be_join_ge)
 hipStream_t g_geStream = nullptr;
 hipEvent_t g_geFork = nullptr, g_geJoin = nullptr;
 bool g_gePending = false;   // (launcher thread only)
@@ -3827,7 +3828,7 @@ bool g_timing = false;
 // the 24 sums); sized at init to the LDS the kernel's static arrays leave
 // free; SGPU_STAGE overrides (0 = read every element from memory)
 uint32_t g_stageCap = 0;
-double g_execMs = 0, g_totalMs = 0;
+double g_totalMs = 0;
 double g_kernelMs[kBeKernelKinds] = {};   // by BeKernel
 
 struct EvPair
@@ -3896,8 +3897,6 @@ void harvest_timing(bool all)
         (void)hipEventElapsedTime(&ms, ev.a, ev.b);
         g_totalMs += ms;
         g_kernelMs[ev.kind] += ms;
-        if (ev.kind == kBeExec)
-            g_execMs += ms;
         g_evFree.push_back(ev);
         g_evUsed.pop_front();
     }
@@ -4236,17 +4235,26 @@ void be_memset(void* dst, int value, size_t bytes)
     check(hipMemsetAsync(dst, value, bytes, g_stream), "memset");
 }
 
-void be_launch_ingest(const IngestDesc* descs, uint32_t count, uint32_t maxBytes, const uint32_t* blocks,
-                      uint32_t nblocks)
+namespace {
+
+// k_ingest on `stream` (the codec stream, or the side stream beside the
+// matrix jobs)
+void launch_ingest(const BeIngest& in, hipStream_t stream)
 {
-    if (count == 0)
+    const uint32_t chunks = in.maxBytes ? (in.maxBytes + kIngestChunkBytes - 1) / kIngestChunkBytes : 1;
+    const uint32_t grid = in.blocks ? in.nblocks : (in.count + kIngestWaves - 1) / kIngestWaves;
+    if (in.count == 0 || grid == 0)
         return;
-    Timed t(kBeIngest);
-    const uint32_t chunks = maxBytes ? (maxBytes + kIngestChunkBytes - 1) / kIngestChunkBytes : 1;
-    const uint32_t grid = blocks ? nblocks : (count + kIngestWaves - 1) / kIngestWaves;
-    if (grid == 0)
-        return;
-    hipLaunchKernelGGL(k_ingest, dim3(grid, chunks), dim3(64 * kIngestWaves), 0, g_stream, descs, count, blocks);
+    Timed t(kBeIngest, stream);
+    hipLaunchKernelGGL(k_ingest, dim3(grid, chunks), dim3(64 * kIngestWaves), 0, stream, in.descs, in.count,
+                       in.blocks);
+}
+
+} // namespace
+
+void be_launch_ingest(const BeIngest& ingest)
+{
+    launch_ingest(ingest, g_stream);
 }
 
 void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStride)
@@ -4277,91 +4285,61 @@ void be_launch_exec(const void* stream, const ExecItem* items, uint32_t count, u
                        reinterpret_cast<unsigned long long*>(acct), results, slots);
 }
 
-void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct)
+void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct, const uint32_t* gates,
+                    const uint32_t* results)
 {
     if (count == 0)
         return;
     Timed t(kBeLdpc);
-    hipLaunchKernelGGL(k_ldpc<false>, dim3(count), dim3(64 * kLdpcWaves), 0, g_stream, items,
-                       reinterpret_cast<unsigned long long*>(acct), (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr);
+    if (!gates)
+        hipLaunchKernelGGL(k_ldpc<false>, dim3(count), dim3(64 * kLdpcWaves), 0, g_stream, items,
+                           reinterpret_cast<unsigned long long*>(acct), (const uint32_t*)nullptr,
+                           (const uint32_t*)nullptr);
+    else
+        hipLaunchKernelGGL(k_ldpc<true>, dim3(count), dim3(64 * kLdpcWaves), 0, g_stream, items,
+                           reinterpret_cast<unsigned long long*>(acct), gates, results);
 }
 
-void be_launch_ldpc_gated(const LdpcItem* items, uint32_t count, uint64_t* acct, const uint32_t* gates,
-                          const uint32_t* results)
+void be_launch_ge(const BeGe& ge, GePlace place, const BeCopy& head)
 {
-    if (count == 0)
+    if (ge.count == 0)
         return;
-    Timed t(kBeLdpc);
-    hipLaunchKernelGGL(k_ldpc<true>, dim3(count), dim3(64 * kLdpcWaves), 0, g_stream, items,
-                       reinterpret_cast<unsigned long long*>(acct), gates, results);
-}
-
-void be_launch_ge(const GeDesc* descs, const uint8_t* in, uint32_t count, uint32_t* results, SolveRow* rows,
-                  uint8_t* coef, uint32_t maxRows, uint32_t maxCols, const BeCopy* head, bool side,
-                  const SolveRow* rowsIn)
-{
-    if (count == 0)
-        return;
-    if (!side) {
-        // in order on the codec stream (be_side_upload_ingest puts the rest
-        // of the upload and k_ingest beside them, after the fork recorded
-        // here)
-        check(hipEventRecord(g_geFork, g_stream), "hipEventRecord(ge fork)");
-        check(hipStreamWaitEvent(g_geStream, g_geFork, 0), "hipStreamWaitEvent(side)");
-        if (head)
-            check(hipMemcpyAsync((void*)(uintptr_t)head->dst, (const void*)(uintptr_t)head->src, head->bytes,
-                                 hipMemcpyHostToDevice, g_stream),
-                  "H2D (ge head)");
-        Timed t(kBeGe);
-        hipLaunchKernelGGL(k_ge, dim3(count), dim3(kGeThreads), (size_t)ge_lds_bytes(maxRows, maxCols), g_stream,
-                           descs, in, results, rows, coef, rowsIn ? rowsIn : rows);
-        return;
-    }
-    // On the side stream: the jobs run beside the codec stream's copy and
-    // k_ingest, which read nothing they write, and be_join_ge puts the codec
-    // stream behind them (Engine::launch_batch joins before the first
-    // k_exec).  Same box, interleaved: headline 4.97 ms/step on the side
-    // stream against 5.34 with the jobs in line on the codec stream
-    // (profiles/r6q_modes_ab.txt).  With `head`, their part of the upload is
-    // copied on the side stream too, beside the codec stream's copy of the
-    // rest (a second copy behind the first on one stream started ~17 us after
-    // it); without, they wait for everything the codec stream queued.
-    if (head) {
-        check(hipMemcpyAsync((void*)(uintptr_t)head->dst, (const void*)(uintptr_t)head->src, head->bytes,
-                             hipMemcpyHostToDevice, g_geStream),
+    // The side stream starts after everything the codec stream queued before
+    // this submission's matrix jobs (an application may pass the output of an
+    // earlier submission as an original: k_ingest must not read it early).
+    check(hipEventRecord(g_geFork, g_stream), "hipEventRecord(ge fork)");
+    check(hipStreamWaitEvent(g_geStream, g_geFork, 0), "hipStreamWaitEvent(ge fork)");
+    // kCodecStream: the jobs in line, be_side_upload_ingest puts the rest of
+    // the upload and k_ingest beside them after the fork (a cross-stream wait
+    // costs 16-23 us before the next kernel even when satisfied, and the join
+    // behind jobs on the side stream waited on a job that ended about when
+    // k_ingest did: profiles/r6l_ge_codec_stream_ab.txt).  kSideStream: the
+    // jobs beside the codec stream's next launches until be_join_ge.
+    const bool side = place == GePlace::kSideStream;
+    hipStream_t stream = side ? g_geStream : g_stream;
+    if (!side && head.bytes)
+        check(hipMemcpyAsync((void*)(uintptr_t)head.dst, (const void*)(uintptr_t)head.src, head.bytes,
+                             hipMemcpyHostToDevice, g_stream),
               "H2D (ge head)");
-    } else {
-        check(hipEventRecord(g_geFork, g_stream), "hipEventRecord(ge fork)");
-        check(hipStreamWaitEvent(g_geStream, g_geFork, 0), "hipStreamWaitEvent(ge)");
-    }
     {
-        Timed t(kBeGe, g_geStream);
-        hipLaunchKernelGGL(k_ge, dim3(count), dim3(kGeThreads), (size_t)ge_lds_bytes(maxRows, maxCols), g_geStream,
-                           descs, in, results, rows, coef, rowsIn ? rowsIn : rows);
+        Timed t(kBeGe, stream);
+        hipLaunchKernelGGL(k_ge, dim3(ge.count), dim3(kGeThreads), (size_t)ge_lds_bytes(ge.maxRows, ge.maxCols),
+                           stream, ge.descs, ge.in, ge.results, ge.rows, ge.coef, ge.rowsIn);
     }
-    check(hipEventRecord(g_geJoin, g_geStream), "hipEventRecord(ge join)");
-    g_gePending = true;
+    if (side) {
+        check(hipEventRecord(g_geJoin, g_geStream), "hipEventRecord(ge join)");
+        g_gePending = true;
+    }
 }
 
-void be_side_upload_ingest(const BeCopy* rest, const IngestDesc* descs, uint32_t count, uint32_t maxBytes,
-                           const uint32_t* blocks, uint32_t nblocks)
+void be_side_upload_ingest(const BeCopy& rest, const BeIngest& ingest)
 {
     bind_device();
-    // after everything the codec stream queued before this submission's
-    // matrix jobs (an application may pass the output of an earlier
-    // submission as an original: k_ingest must not read it early); the jobs
-    // were queued after this fork point, so the two run side by side
-    if (rest && rest->bytes)
-        check(hipMemcpyAsync((void*)(uintptr_t)rest->dst, (const void*)(uintptr_t)rest->src, rest->bytes,
+    if (rest.bytes)
+        check(hipMemcpyAsync((void*)(uintptr_t)rest.dst, (const void*)(uintptr_t)rest.src, rest.bytes,
                              hipMemcpyHostToDevice, g_geStream),
               "H2D (upload rest)");
-    const uint32_t chunks = maxBytes ? (maxBytes + kIngestChunkBytes - 1) / kIngestChunkBytes : 1;
-    const uint32_t grid = blocks ? nblocks : (count + kIngestWaves - 1) / kIngestWaves;
-    if (count && grid) {
-        Timed t(kBeIngest, g_geStream);
-        hipLaunchKernelGGL(k_ingest, dim3(grid, chunks), dim3(64 * kIngestWaves), 0, g_geStream, descs, count, blocks);
-    }
+    launch_ingest(ingest, g_geStream);
     check(hipEventRecord(g_geJoin, g_geStream), "hipEventRecord(side join)");
     g_gePending = true;
 }
@@ -4445,11 +4423,12 @@ void be_launch_solve(const SolveDesc* solves, const SolveRow* rows, const uint8_
 // valid length prefixes and zero bytes past their lengths, as the decoder's
 // recovered originals do (with `corrupt`, every third solve gets non-zero
 // bytes past one row's length: inconsistent recovery data), forms the rows
-// R = L U X the sweeps invert, and runs the sweeps, the vector product and the
-// matrix-core product on copies of them.  stats[0..1]: bytes of the rows (and
-// result words [0..m]) where the vector / matrix-core product's outcome differs
-// from the sweeps'; stats[2..3]: solves those two flagged for the sweeps.
-// Returns 0 when both match the sweeps, 1 when not, -1 on a device error.
+// R = L U X the sweeps invert, and runs the sweeps and the vector product on
+// copies of them.  stats[0]: bytes of the rows (and result words [0..m])
+// where the vector product's outcome differs from the sweeps'; stats[2]:
+// solves it flagged for the sweeps (stats[1] and stats[3] read zero: no
+// second product path is built).  Returns 0 when the product matches the
+// sweeps, 1 when not, -1 on a device error.
 extern "C" __attribute__((visibility("default"))) int sgpu_selftest_solve_paths(uint32_t seed, uint32_t nsolves,
                                                                                 uint32_t corrupt,
                                                                                 uint32_t* stats)
@@ -4834,10 +4813,8 @@ void be_timing_reset()
 {
     for (double& v : g_kernelMs)
         v = 0;
-    g_execMs = 0;
     g_totalMs = 0;
 }
-double be_timing_exec_ms() { return g_execMs; }
 double be_timing_total_ms() { return g_totalMs; }
 
 } // namespace sgpu

@@ -293,11 +293,6 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_range(SgpuDecoder decoder, uns
         stride == 0 || (stride & 15u) || (uint64_t)stride > (1ull << 32) || (lens & 3u) ||
         firstPacketNum > SIAMESE_PACKET_NUM_MAX)
         return Siamese_InvalidInput;
-    if (!be_has_deliver()) {
-        // (a missing kernel is an error, never a quiet no-op: backend.h)
-        std::fprintf(stderr, "siamese_amd: this backend has no delivery kernel (be_launch_deliver)\n");
-        return Siamese_Disabled;
-    }
     unsigned queued = 0;
     const SiameseResult r =
         BD(decoder)->core.deliver_range(firstPacketNum, count, dst, (uint64_t)stride, lens, results, &queued);
@@ -586,7 +581,7 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 {
     be_timing_enable(enable != 0);
     if (execMs)
-        *execMs = be_timing_exec_ms();
+        *execMs = be_timing_kernel_ms(kBeExec);
     if (totalMs)
         *totalMs = be_timing_total_ms();
     if (reset)

@@ -2145,7 +2145,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
             sv.solveCount = sdescs.size() - sv.solveBegin;
             if (solve_split((uint32_t)sv.solveCount, sv.maxRows))
                 for (size_t i = sv.solveBegin; i < sdescs.size(); ++i) {
-                    // the inverse's scratch (matrix-core path), in the k_ldpc ring
+                    // the inverse's scratch (k_solve_pre's T), in the k_ldpc ring
                     // after this submission's k_ldpc scratch (1 + its offset
                     // there until placed below)
                     const uint32_t tb = solve_t_bytes(sdescs[i].m);
@@ -2524,15 +2524,6 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     st.assembleNs = now_ns() - t0;
 }
 
-// The matrix jobs in order on the codec stream, the rest of the upload and
-// k_ingest beside them (launch_batch).  Traces of both arrangements
-// (tools/r6_trace_libs.sh): a round's first k_exec starts 150 us after its
-// first copy against 157 with the jobs on the side stream; a cross-stream
-// wait costs 16-23 us before the next kernel even when satisfied, and a
-// kernel starts 12-20 us after a copy on its queue.  Headline within noise
-// (profiles/r6l_ge_codec_stream_ab.txt).
-constexpr bool kGeOnCodecStream = true;
-
 void Engine::launch_batch(Batch& bt)
 {
     XferSet& xs = sets_[bt.set];
@@ -2545,52 +2536,52 @@ void Engine::launch_batch(Batch& bt)
     }
     bt.marks.clear();
     // The upload.  With matrix jobs its head (the jobs' inputs and the solve
-    // rows and coefficients they rewrite) is copied first and the jobs run on
-    // it in order on the codec stream, while the rest of the upload and
-    // k_ingest run beside them on the side stream, joined before the first
-    // phase.  (The other way round -- the jobs on the side stream -- the
-    // codec stream's join waited on a job that ended about when k_ingest did,
-    // and a cross-stream wait that is not yet satisfied costs ~24 us of
-    // latency on the join; a satisfied one costs next to nothing.)
+    // rows and coefficients they rewrite) goes first and the jobs run on it in
+    // line on the codec stream, while the rest of the upload and k_ingest run
+    // beside them on the side stream, joined before the first phase.  Traces
+    // of this and of the jobs on the side stream: a round's first k_exec
+    // starts 150 us after its first copy against 157, and a kernel starts
+    // 12-20 us after a copy on its queue; headline within noise
+    // (profiles/r6l_ge_codec_stream_ab.txt).
     const bool copyUp = bt.upBytes && bt.upBase == xs.upDev;
     const size_t head = (copyUp && bt.nGe) ? bt.geHead : 0;
     uint64_t* acctDev = (uint64_t*)xs.downDev;
     uint32_t* resultsDev = (uint32_t*)(xs.downDev + kAcctBytes);
     const BeCopy rest{(uint64_t)(uintptr_t)xs.upDev + head, (uint64_t)(uintptr_t)xs.upHost + head,
                       bt.upBytes - head};
-    bool ingested = false;
-    if (bt.nGe && head && kGeOnCodecStream && bt.allGated && xs.upHostDev) {
-        // Every solve here is a chained job's, so nothing in the head needs
-        // the copy: the jobs read their descriptors, inputs and solve rows
-        // from the pinned upload over the bus and write the solves' rows and
-        // coefficients to the device copy, starting at once (a kernel starts
-        // 12-20 us after a copy on its queue): a round's first k_exec 148 ->
-        // 118 us after its first copy (profiles/r6m_ge_zero_copy_ab.txt).
-        const uint8_t* hd = xs.upHostDev;
-        be_launch_ge((const GeDesc*)(hd + bt.oGeD), hd + bt.oGeIn, (uint32_t)bt.nGe, resultsDev,
-                     (SolveRow*)(bt.upBase + bt.oSR), bt.upBase + bt.oCoef, bt.geMaxRows, bt.geMaxCols, nullptr,
-                     false, (const SolveRow*)(hd + bt.oSR));
-        be_side_upload_ingest(bt.upBytes > head ? &rest : nullptr, (const IngestDesc*)(bt.upBase + bt.oIngD),
-                              (uint32_t)bt.nIngest, bt.maxIngest, (const uint32_t*)(bt.upBase + bt.oIngB),
-                              (uint32_t)bt.nIngBlocks);
-        ingested = true;
-    } else if (bt.nGe) {
-        const BeCopy hc{(uint64_t)(uintptr_t)xs.upDev, (uint64_t)(uintptr_t)xs.upHost, head};
-        be_launch_ge((const GeDesc*)(bt.upBase + bt.oGeD), bt.upBase + bt.oGeIn, (uint32_t)bt.nGe, resultsDev,
-                     (SolveRow*)(bt.upBase + bt.oSR), bt.upBase + bt.oCoef, bt.geMaxRows, bt.geMaxCols,
-                     head ? &hc : nullptr, !(head && kGeOnCodecStream));
-        if (head && kGeOnCodecStream) {
-            be_side_upload_ingest(bt.upBytes > head ? &rest : nullptr, (const IngestDesc*)(bt.upBase + bt.oIngD),
-                                  (uint32_t)bt.nIngest, bt.maxIngest, (const uint32_t*)(bt.upBase + bt.oIngB),
-                                  (uint32_t)bt.nIngBlocks);
-            ingested = true;
-        }
+    const BeIngest ingest{(const IngestDesc*)(bt.upBase + bt.oIngD), (uint32_t)bt.nIngest, bt.maxIngest,
+                          (const uint32_t*)(bt.upBase + bt.oIngB), (uint32_t)bt.nIngBlocks};
+    // the jobs with their descriptors, inputs and the rows they read at `up`
+    // (they always write the rows and coefficients of the device's upload)
+    auto ge_at = [&](const uint8_t* up) {
+        return BeGe{(const GeDesc*)(up + bt.oGeD), up + bt.oGeIn, (uint32_t)bt.nGe, resultsDev,
+                    (const SolveRow*)(up + bt.oSR), (SolveRow*)(bt.upBase + bt.oSR), bt.upBase + bt.oCoef,
+                    bt.geMaxRows, bt.geMaxCols};
+    };
+    if (head && bt.allGated && xs.upHostDev) {
+        // 1. Every solve here is a chained job's, so nothing in the head
+        // needs the copy: the jobs read their descriptors, inputs and solve
+        // rows from the pinned upload over the bus, starting at once: a
+        // round's first k_exec 148 -> 118 us after its first copy
+        // (profiles/r6m_ge_zero_copy_ab.txt).
+        be_launch_ge(ge_at(xs.upHostDev), GePlace::kCodecStream);
+        be_side_upload_ingest(rest, ingest);
+    } else if (head) {
+        // 2. The head is copied ahead of the jobs.
+        be_launch_ge(ge_at(bt.upBase), GePlace::kCodecStream,
+                     BeCopy{(uint64_t)(uintptr_t)xs.upDev, (uint64_t)(uintptr_t)xs.upHost, head});
+        be_side_upload_ingest(rest, ingest);
+    } else {
+        // 3. No copied head (no jobs, or an upload the kernels read in
+        // place): the jobs run on the side stream while the codec stream
+        // carries on.
+        if (bt.nGe)
+            be_launch_ge(ge_at(bt.upBase), GePlace::kSideStream);
+        if (copyUp)
+            be_copy_pinned(&rest, 1, true);
+        be_launch_ingest(ingest);
     }
-    if (!ingested && copyUp && bt.upBytes > head)
-        be_copy_pinned(&rest, 1, true);
-    if (!ingested && bt.nIngest)
-        be_launch_ingest((const IngestDesc*)(bt.upBase + bt.oIngD), (uint32_t)bt.nIngest, bt.maxIngest,
-                         (const uint32_t*)(bt.upBase + bt.oIngB), (uint32_t)bt.nIngBlocks);
+    const bool ingested = head != 0;   // (k_ingest ran on the side stream)
     if (xs.acctZero) {
         be_memset(acctDev, 0, 4 * sizeof(uint64_t));
         xs.acctZero = false;
@@ -2609,11 +2600,8 @@ void Engine::launch_batch(Batch& bt)
     if (wideDone) {
         if (ingested || wideGates)
             be_join_ge();   // (its items and the elements they read came with the side stream)
-        if (wideGates)
-            be_launch_ldpc_gated((const LdpcItem*)(bt.upBase + bt.oWide), (uint32_t)wideDone, acctDev + 3, wideGates,
-                                 resultsDev);
-        else
-            be_launch_ldpc((const LdpcItem*)(bt.upBase + bt.oWide), (uint32_t)wideDone, acctDev + 3);
+        be_launch_ldpc((const LdpcItem*)(bt.upBase + bt.oWide), (uint32_t)wideDone, acctDev + 3, wideGates,
+                       resultsDev);
     }
     // The codec stream joins the matrix jobs before the first executor launch
     // (they run beside k_ingest): joined only before the decoders' phases,
@@ -2623,14 +2611,9 @@ void Engine::launch_batch(Batch& bt)
     for (const Phase& ph : bt.phases) {
         be_join_ge();   // (no-op once joined)
         if (ph.kind == Phase::EXEC) {
-            if (ph.wideCount && ph.wideBegin >= wideDone) {
-                const LdpcItem* items = (const LdpcItem*)(bt.upBase + bt.oWide) + ph.wideBegin;
-                if (wideGates)
-                    be_launch_ldpc_gated(items, (uint32_t)ph.wideCount, acctDev + 3, wideGates + ph.wideBegin,
-                                         resultsDev);
-                else
-                    be_launch_ldpc(items, (uint32_t)ph.wideCount, acctDev + 3);
-            }
+            if (ph.wideCount && ph.wideBegin >= wideDone)
+                be_launch_ldpc((const LdpcItem*)(bt.upBase + bt.oWide) + ph.wideBegin, (uint32_t)ph.wideCount,
+                               acctDev + 3, wideGates ? wideGates + ph.wideBegin : nullptr, resultsDev);
             be_launch_exec(bt.upBase + bt.oStream, (const ExecItem*)(bt.upBase + bt.oItems) + ph.itemBegin,
                            (uint32_t)ph.itemCount, acctDev, resultsDev, ph.maxRows);
             st.execLaunches++;
@@ -2647,15 +2630,8 @@ void Engine::launch_batch(Batch& bt)
     // the symbols are final, a recovered packet's length prefix included, and
     // every buffer a call of this submission released is still untouched
     // (released buffers return to the arena in reclaim_batch, after the fence).
-    if (bt.nDeliver) {
-        // (sgpu_decoder_deliver_range queues nothing on a backend without the
-        // kernel, backend.h: items that got here anyway fail the engine)
-        if (be_has_deliver())
-            be_launch_deliver((const DeliverItem*)(bt.upBase + bt.oDeliver), (uint32_t)bt.nDeliver,
-                              bt.maxDeliverStride);
-        else
-            failed_.store(true, std::memory_order_relaxed);
-    }
+    if (bt.nDeliver)
+        be_launch_deliver((const DeliverItem*)(bt.upBase + bt.oDeliver), (uint32_t)bt.nDeliver, bt.maxDeliverStride);
     // the counters and solve results, then the downloads, in one call (one
     // kernel when small; its range list was laid out with the upload: a
     // drop-in submission carries a range per application call)
@@ -2960,7 +2936,7 @@ bool Engine::gather(unsigned count, const void* const* srcs, const unsigned* byt
     uint32_t maxBytes = 0;
     for (unsigned i = 0; i < count; ++i)
         maxBytes = std::max(maxBytes, bytes[i]);
-    be_launch_ingest((const IngestDesc*)gUpDev_, count, maxBytes);
+    be_launch_ingest(BeIngest{(const IngestDesc*)gUpDev_, count, maxBytes});
     be_d2h(gHost_, gDev_, total);
     const bool ok = be_sync();
     if (!ok) {

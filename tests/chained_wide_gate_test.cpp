@@ -11,8 +11,8 @@
 //            scratch pair are untouched, and only the ungated picks count.
 //   "open"   without the hook the job succeeds and both rows run.
 //
-// Linked with the hostsim backend (tests/hostsim/backend_hostsim.cpp and
-// backend_hostsim_gate.cpp), gf.cpp and codedef.cpp.
+// Linked with the hostsim backend (tools/backend_hostsim.cpp), gf.cpp
+// and codedef.cpp.
 #include "backend.h"
 #include "codedef.h"
 #include "gf.h"
@@ -166,11 +166,11 @@ int main(int argc, char** argv)
 
     // the submission: the job, then k_ldpc with the gate array, then k_exec
     uint64_t acct[4] = {0, 0, 0, 0};
-    be_launch_ge(&gd, geIn.data(), 1, results.data(), &srow, &coef, 1, 1, nullptr, false);
+    be_launch_ge(BeGe{&gd, geIn.data(), 1, results.data(), &srow, &srow, &coef, 1, 1}, GePlace::kCodecStream);
     be_join_ge();
     if (results[okWord] != (open ? 1u : 0u))
         return fail(open ? "the job did not succeed" : "the hook did not force outcome 0");
-    be_launch_ldpc_gated(items, 2, acct + 3, gates, results.data());
+    be_launch_ldpc(items, 2, acct + 3, gates, results.data());
     be_launch_exec(stream.data(), &ex, 1, acct, results.data(), E);
 
     uint8_t l0[kBytes], l1[kBytes], out[kBytes];

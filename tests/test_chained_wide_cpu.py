@@ -159,14 +159,8 @@ def test_gate_unit_on_hostsim(tmp_path):
     exe = tmp_path / "chained_wide_gate_test"
     csrc = os.path.join(ROOT, "siamese_amd", "csrc")
     flags = ["-O1", "-std=c++17", "-mavx2", "-pthread", "-I", csrc, "-I", os.path.join(ROOT, "include")]
-    # (as siamese_amd/Makefile builds the hostsim backend: its be_launch_ge
-    # under the hook of backend_hostsim_gate.cpp)
-    sim = tmp_path / "backend_hostsim.o"
-    subprocess.run(["g++"] + flags + ["-Dbe_launch_ge=be_launch_ge_plain", "-c",
-                                      os.path.join(ROOT, "tests", "hostsim", "backend_hostsim.cpp"),
-                                      "-o", str(sim)], check=True, timeout=300)
-    subprocess.run(["g++"] + flags + [os.path.join(ROOT, "tests", "chained_wide_gate_test.cpp"), str(sim),
-                                      os.path.join(ROOT, "tests", "hostsim", "backend_hostsim_gate.cpp"),
+    subprocess.run(["g++"] + flags + [os.path.join(ROOT, "tests", "chained_wide_gate_test.cpp"),
+                                      os.path.join(ROOT, "tools", "backend_hostsim.cpp"),
                                       os.path.join(csrc, "gf.cpp"), os.path.join(csrc, "codedef.cpp"),
                                       "-o", str(exe)], check=True, timeout=300)
     env = dict(os.environ, SGPU_TEST_GE_FORCE_SINGULAR="1")

@@ -97,7 +97,6 @@ def test_sequences_under_sanitizers(tmp_path):
     built with -fsanitize=address,undefined (and SGPU_WALK_CHECK) into one
     stand-alone program: no report, and the reference's event logs."""
     csrc = os.path.join(ROOT, "siamese_amd", "csrc")
-    sim = os.path.join(ROOT, "tests", "hostsim")
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
     flags = ["-std=c++17", "-O1", "-g", "-mavx2", "-fvisibility=hidden",
              "-DSGPU_WALK_CHECK"] + san
@@ -105,14 +104,10 @@ def test_sequences_under_sanitizers(tmp_path):
             "arq.cpp", "api.cpp", "batch.cpp", "frames.cpp"]
     jobs = []
     objs = []
-    for src in [os.path.join(csrc, f) for f in host] + [os.path.join(sim, "backend_hostsim_gate.cpp")]:
+    for src in [os.path.join(csrc, f) for f in host] + [os.path.join(ROOT, "tools", "backend_hostsim.cpp")]:
         obj = str(tmp_path / (os.path.basename(src) + ".o"))
         objs.append(obj)
         jobs.append(subprocess.Popen(["g++"] + flags + ["-c", src, "-o", obj]))
-    obj = str(tmp_path / "backend_hostsim.o")
-    objs.append(obj)
-    jobs.append(subprocess.Popen(["g++"] + flags + ["-Dbe_launch_ge=be_launch_ge_plain", "-c",
-                                                    os.path.join(sim, "backend_hostsim.cpp"), "-o", obj]))
     for j in jobs:
         assert j.wait(timeout=600) == 0
     # one program with the sanitizers' runtimes linked in: it needs nothing

@@ -1,4 +1,4 @@
-// tests/hostsim/backend_hostsim.cpp -- TEST INFRASTRUCTURE ONLY.
+// tools/backend_hostsim.cpp -- TEST INFRASTRUCTURE ONLY.
 //
 // A CPU simulation of the backend.h contract, used solely by the CPU test
 // suite to exercise the host control plane (encoder/decoder/engine) on a
@@ -7,9 +7,9 @@
 // only backend is backend_hip.hip.  The kernels' byte semantics are restated
 // here one lane-tile at a time (including the v_perm_b32 GF(256) multiply),
 // so a wrong op stream or table fails the same parity tests the GPU runs.
-#include "../../siamese_amd/csrc/backend.h"
-#include "../../siamese_amd/csrc/gf.h"
-#include "../../siamese_amd/csrc/codedef.h"
+#include "../siamese_amd/csrc/backend.h"
+#include "../siamese_amd/csrc/gf.h"
+#include "../siamese_amd/csrc/codedef.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -371,20 +371,21 @@ static void ingest_one(const IngestDesc& run, uint32_t k)
 
 // The kernel's work assignment, block by block (a symbol the host's block
 // table misses is not copied here either)
-void be_launch_ingest(const IngestDesc* descs, uint32_t count, uint32_t, const uint32_t* blocks, uint32_t nblocks)
+void be_launch_ingest(const BeIngest& in)
 {
     if (noexec())
         return;
-    if (!blocks) {
-        for (uint32_t i = 0; i < count; ++i)
-            ingest_one(descs[i], 0);
+    if (!in.blocks) {
+        for (uint32_t i = 0; i < in.count; ++i)
+            ingest_one(in.descs[i], 0);
         return;
     }
-    for (uint32_t b = 0; b < nblocks; ++b) {
+    const uint32_t* blocks = in.blocks;
+    for (uint32_t b = 0; b < in.nblocks; ++b) {
         const uint32_t di = blocks[b] >> 4;
-        if (di >= count)
+        if (di >= in.count)
             continue;
-        const IngestDesc& d = descs[di];
+        const IngestDesc& d = in.descs[di];
         const uint32_t n = d.count ? d.count : 1u;
         for (uint32_t w = 0; w < kIngestWaves; ++w) {
             const uint32_t k = (blocks[b] & 15u) * kIngestWaves + w;
@@ -418,11 +419,15 @@ void be_launch_exec(const void* stream, const ExecItem* items, uint32_t count, u
                       (exec_first_tile(items[i].tiles) + t) * kExecTileBytes, acct, results);
 }
 
-void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct)
+void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct, const uint32_t* gates,
+                    const uint32_t* results)
 {
     if (noexec())
         return;
     for (uint32_t k = 0; k < count; ++k) {
+        // (a gated item of a chained elimination that failed is not run at all)
+        if (gates && gates[k] != 0 && results[gates[k] - 1] == 0)
+            continue;
         const LdpcItem& it = items[k];
         const WinEntry* win = reinterpret_cast<const WinEntry*>((uintptr_t)it.win);
         Pcg32 prng;
@@ -438,6 +443,35 @@ void be_launch_ldpc(const LdpcItem* items, uint32_t count, uint64_t* acct)
             for (uint32_t b = it.tileBase; b < t1 && b < x.len; ++b)
                 dst[b] ^= P(x.src)[b];
         }
+    }
+}
+
+// k_deliver (ops.h DeliverItem): the prefix is read from the symbol (reference
+// SiameseSerializers.h:598-640), checked against the symbol's readable bytes
+// and the row, and the row gets the payload and a zero tail; an absent packet
+// only its zero length word.
+void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t)
+{
+    if (noexec())
+        return;
+    for (uint32_t i = 0; i < count; ++i) {
+        const DeliverItem& it = items[i];
+        const uint64_t stride = (uint64_t)it.stride16 << 4;
+        unsigned h = 0, L = 0;
+        if (it.src != 0 && it.cap != 0) {
+            unsigned len = 0;
+            const int hh = parse_prefix(P(it.src), it.cap < 4 ? it.cap : 4, &len);
+            if (hh >= 1 && len >= 1 && (unsigned)hh + len <= it.cap && len <= stride) {
+                h = (unsigned)hh;
+                L = len;
+            }
+        }
+        const uint32_t lw = L;
+        std::memcpy(P(it.lenOut), &lw, 4);
+        if (it.src == 0)
+            continue;
+        for (uint64_t b = 0; b < stride; ++b)
+            P(it.dst)[b] = b < L ? P(it.src)[h + b] : 0;
     }
 }
 
@@ -575,7 +609,7 @@ bool be_gather(const IngestDesc* descsHost, void* descsDev, uint32_t count, cons
 {
     *packed = *landed = reinterpret_cast<void*>(1);
     std::memcpy(descsDev, descsHost, (size_t)count * sizeof(IngestDesc));
-    be_launch_ingest(static_cast<const IngestDesc*>(descsDev), count, 0);
+    be_launch_ingest(BeIngest{static_cast<const IngestDesc*>(descsDev), count, 0});
     std::memcpy(hostOut, devStage, bytes);
     return true;
 }
@@ -599,9 +633,7 @@ bool be_fence_wait(void*, unsigned, bool) { return be_sync(); }
 void be_timing_enable(bool) {}
 void be_timing_reset() {}
 double be_timing_kernel_ms(BeKernel) { return 0; }
-double be_timing_exec_ms() { return 0; }
 double be_timing_total_ms() { return 0; }
-
 
 void be_launch_solve(const SolveDesc* solves, const SolveRow* rows, const uint8_t* coef, uint32_t* results,
                      const SolveItem* items, uint32_t count, uint32_t maxRows, uint64_t* acct,
@@ -615,29 +647,30 @@ void be_launch_solve(const SolveDesc* solves, const SolveRow* rows, const uint8_
     solve_main(solves, rows, coef, results, items, count, maxRows);
 }
 
+// (the side stream is the caller's thread here)
+void be_side_upload_ingest(const BeCopy& rest, const BeIngest& ingest)
+{
+    if (rest.bytes)
+        be_copy_pinned(&rest, 1, true);
+    be_launch_ingest(ingest);
+}
+
 // k_ge: a fresh recovery matrix from its job (generation as the host's
 // generate_matrix, reference SiameseDecoder.cpp:2157-2383), then the
 // elimination without pivoting while the pivots allow it and with row
 // pivoting from the first zero pivot (:2423-2531), as the kernel runs it.
-void be_side_upload_ingest(const BeCopy* rest, const IngestDesc* descs, uint32_t count, uint32_t maxBytes,
-                           const uint32_t* blocks, uint32_t nblocks)
+// SGPU_TEST_GE_FORCE_SINGULAR=1 (a test hook) then makes every chained job
+// report a singular matrix (outcome word 0, stopped at pivot 0).  What a
+// successful job wrote for its solve stays, as that solve is gated on the
+// outcome and does not run.
+void be_launch_ge(const BeGe& ge, GePlace place, const BeCopy& head)
 {
-    if (rest)
-        be_copy_pinned(rest, 1, true);
-    be_launch_ingest(descs, count, maxBytes, blocks, nblocks);
-}
-
-void be_launch_ge(const GeDesc* descs, const uint8_t* in, uint32_t count, uint32_t* results, SolveRow* srows,
-                  uint8_t* scoef, uint32_t, uint32_t, const BeCopy* head, bool, const SolveRow* srowsIn)
-{
-    if (!srowsIn)
-        srowsIn = srows;
-    if (head)
-        be_copy_pinned(head, 1, true);
-    for (uint32_t jb = 0; jb < count; ++jb) {
-        const GeDesc d = descs[jb];
+    if (place == GePlace::kCodecStream && head.bytes)
+        be_copy_pinned(&head, 1, true);
+    for (uint32_t jb = 0; jb < ge.count; ++jb) {
+        const GeDesc d = ge.descs[jb];
         const unsigned rows = d.rows, cols = d.cols;
-        const GeRow* R = reinterpret_cast<const GeRow*>(in + d.in);
+        const GeRow* R = reinterpret_cast<const GeRow*>(ge.in + d.in);
         const GeCol* C = reinterpret_cast<const GeCol*>(R + rows);
         const uint8_t* pick = reinterpret_cast<const uint8_t*>(C + cols);
         std::vector<uint8_t> M((size_t)rows * cols, 0);
@@ -731,7 +764,7 @@ void be_launch_ge(const GeDesc* descs, const uint8_t* in, uint32_t count, uint32
             for (unsigned j = 0; j < cols; ++j)
                 for (unsigned i = 0; i < j; ++i)
                     nz += M[(size_t)piv[j] * cols + i] != 0;
-        uint32_t* out = results + d.result;
+        uint32_t* out = ge.results + d.result;
         std::memset(out, 0, kGeOutHeader * 4);
         out[0] = stop;
         out[1] = (uint32_t)bytes;
@@ -745,11 +778,11 @@ void be_launch_ge(const GeDesc* descs, const uint8_t* in, uint32_t count, uint32
                 po[i] = piv[i];
             if (!ok)
                 continue;
-            uint8_t* co = scoef + d.solveCoef;
+            uint8_t* co = ge.coef + d.solveCoef;
             for (unsigned j = 0; j < cols; ++j)
                 std::memcpy(co + (size_t)j * cols, &M[(size_t)piv[j] * cols], cols);
-            SolveRow* sr = srows + d.solveRow;
-            std::vector<SolveRow> t(srowsIn + d.solveRow, srowsIn + d.solveRow + cols);
+            SolveRow* sr = ge.rows + d.solveRow;
+            std::vector<SolveRow> t(ge.rowsIn + d.solveRow, ge.rowsIn + d.solveRow + cols);
             for (unsigned j = 0; j < cols; ++j) {
                 sr[j] = t[piv[j]];
                 sr[j].headIndex = 1 + solve_head_slot(t[piv[j]].headIndex, piv[j]);
@@ -770,6 +803,16 @@ void be_launch_ge(const GeDesc* descs, const uint8_t* in, uint32_t count, uint32
         std::memset(mo, 0, 4 * ((rows * cols + 3) / 4));
         std::memcpy(mo, M.data(), M.size());
     }
+    // (read per launch, so one test process can switch it)
+    const char* force = std::getenv("SGPU_TEST_GE_FORCE_SINGULAR");
+    if (!force || std::atol(force) == 0)
+        return;
+    for (uint32_t k = 0; k < ge.count; ++k)
+        if (ge.descs[k].flags & kGeChained) {
+            uint32_t* out = ge.results + ge.descs[k].result;
+            out[0] = 0;   // the first pivot without a non-zero
+            out[3] = 0;   // the outcome the gates read
+        }
 }
 
 // (synchronous here)

@@ -81,10 +81,9 @@ void be_copy_pinned(const BeCopy* r, unsigned n, bool toDevice)
 void be_copy_list(const BeCopy* r, const void*, unsigned n, bool toDevice) { be_copy_pinned(r, n, toDevice); }
 void be_memset(void* dst, int value, size_t bytes) { std::memset(dst, value, bytes); }
 
-void be_launch_ingest(const IngestDesc*, uint32_t, uint32_t, const uint32_t*, uint32_t) {}
+void be_launch_ingest(const BeIngest&) {}
 void be_launch_exec(const void*, const ExecItem*, uint32_t, uint64_t*, const uint32_t*, uint32_t) {}
-void be_launch_ldpc(const LdpcItem*, uint32_t, uint64_t*) {}
-void be_launch_ldpc_gated(const LdpcItem*, uint32_t, uint64_t*, const uint32_t*, const uint32_t*) {}
+void be_launch_ldpc(const LdpcItem*, uint32_t, uint64_t*, const uint32_t*, const uint32_t*) {}
 void be_launch_deliver(const DeliverItem*, uint32_t, uint32_t) {}
 
 static void solve_prefix(const SolveDesc* solves, const SolveRow*, const uint8_t*,
@@ -129,7 +128,6 @@ bool be_fence_wait(void*, unsigned, bool) { return true; }
 void be_timing_enable(bool) {}
 void be_timing_reset() {}
 double be_timing_kernel_ms(BeKernel) { return 0; }
-double be_timing_exec_ms() { return 0; }
 double be_timing_total_ms() { return 0; }
 
 
@@ -148,21 +146,20 @@ void be_launch_solve(const SolveDesc* solves, const SolveRow* rows, const uint8_
 
 // matrix jobs: every one reports an eliminated matrix with identity pivots,
 // its first `cols` rows used and zero coefficients (no elimination on the host)
-void be_side_upload_ingest(const BeCopy* rest, const IngestDesc*, uint32_t, uint32_t, const uint32_t*, uint32_t)
+void be_side_upload_ingest(const BeCopy& rest, const BeIngest&)
 {
-    if (rest)
-        be_copy_pinned(rest, 1, true);
+    if (rest.bytes)
+        be_copy_pinned(&rest, 1, true);
 }
 
-void be_launch_ge(const GeDesc* descs, const uint8_t*, uint32_t count, uint32_t* results, SolveRow*, uint8_t*,
-                  uint32_t, uint32_t, const BeCopy* head, bool, const SolveRow*)
+void be_launch_ge(const BeGe& ge, GePlace place, const BeCopy& head)
 {
-    if (head)
-        be_copy_pinned(head, 1, true);
-    const GeDesc* dd = host_view(descs);
-    for (uint32_t j = 0; j < count; ++j) {
+    if (place == GePlace::kCodecStream && head.bytes)
+        be_copy_pinned(&head, 1, true);
+    const GeDesc* dd = host_view(ge.descs);
+    for (uint32_t j = 0; j < ge.count; ++j) {
         const GeDesc d = dd[j];
-        uint32_t* out = results + d.result;
+        uint32_t* out = ge.results + d.result;
         const bool chained = (d.flags & kGeChained) != 0;
         std::memset(out, 0, (size_t)ge_result_words(d.rows, d.cols, chained) * 4);
         out[0] = d.cols;
