@@ -194,8 +194,9 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_get_range(SgpuDecoder decoder, unsigne
 /// the delivery reads the symbols after every other device launch of its
 /// submission, and a symbol that a later call of the same submission drops
 /// (the window sliding on, the decoder freed) is recycled only after the
-/// submission has completed.  Delivery of an encoder's recovery packets and a
-/// list (non-range) form are not offered.
+/// submission has completed.  An encoder's packets leave through
+/// sgpu_encoder_deliver_range / sgpu_frames_deliver_recovery (below); a list
+/// (non-range) form is not offered.
 SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_range(SgpuDecoder decoder, unsigned firstPacketNum, unsigned count,
                                                         void* deviceDst, size_t stride, unsigned* deviceLens,
                                                         SiameseResult* results /* host, optional */,
@@ -334,13 +335,87 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv(const SgpuDecoder* decoders, unsig
 SIAMESE_EXPORT long long sgpu_frames_send(unsigned count, const SgpuRecoveryPacket* packets, const unsigned* flows,
                                           void* pinnedOut, size_t capacity, size_t* bytesOut);
 
+/*
+    Packets out of the sender, into caller-owned device rows: the wire
+    datagrams of a stream, originals and recovery packets, placed by the same
+    submission that encodes them, without a second device pass and without
+    waiting (sgpu_frames_send gathers packets of completed submissions into
+    host memory; the originals it cannot frame at all).
+
+    Row contract of both calls: row k starts at deviceDst + k*stride.  Bytes
+    [0, h) are the frame header exactly as sgpu_frame_write_header writes it
+    (h = 0 for a bare packet), bytes [h, h+n) the packet -- a recovery packet's
+    payload and footer (n = DataBytes), an original's payload without its
+    symbol length prefix -- and bytes [h+n, stride) are zero; deviceLens[k] =
+    h+n (uint32, device memory).  Rows are multiples of 16 bytes with zero
+    tails, so the whole buffer read as one byte string is a valid frame stream
+    for sgpu_frames_parse / sgpu_frames_recv: ready for one copy to the host,
+    for a NIC that reads device memory, or for a decoder on the same GPU.
+
+    Neither call ever waits for the GPU: rows and lengths are in place when
+    the submission that carries the call completes (sgpu_flush / sgpu_wait /
+    sgpu_query == 1).  A recovery packet made by an sgpu_encode of the same
+    submission is delivered from its final bytes, an original added in the same
+    submission is delivered too.
+
+    Siamese_InvalidInput, with nothing queued: null deviceDst or deviceLens
+    with count > 0; deviceDst not 16-byte aligned; stride zero, not a multiple
+    of 16 or above 4 GiB; deviceLens not 4-byte aligned; a flow above 2^24-1
+    other than SGPU_FRAME_NONE; any packet whose h+n exceeds stride (every
+    length is known on the host, so this is always caught by the call).
+    count == 0 returns Siamese_Success with *queuedOut = 0.
+
+    The caller guarantees that nothing else reads or writes the rows or the
+    lengths from the call until that submission completes; two deliveries into
+    overlapping rows in one submission are undefined.  The arena's lifetime
+    rule needs no thought here: the frames are read after every other device
+    launch of their submission, and a packet that a later call of the same
+    submission drops (the next sgpu_encode, sgpu_encoder_remove_before, the
+    encoder freed) is recycled only after the submission has completed.
+*/
+/// No frame header: rows hold the bare packet (flow argument of the calls below).
+#define SGPU_FRAME_NONE 0xffffffffu
+
+/// Queue `count` recovery packets (as sgpu_encode / sgpu_encode_range returned
+/// them, each still its encoder's current output) into caller-owned device
+/// rows, packet k framed as SGPU_FRAME_RECOVERY for flows[k] (flows == NULL, or
+/// flows[k] == SGPU_FRAME_NONE: the bare packet).  Touches each packet's
+/// producing encoder, the same threading rule as sgpu_decoder_add_recovery.
+/// Also Siamese_InvalidInput, every packet being checked before any is queued:
+/// null packets with count > 0; a packet with null DeviceData, null Producer,
+/// or DataBytes of 0 or more than SIAMESE_MAX_PACKET_BYTES.  Siamese_Disabled
+/// once the device has failed.  *queuedOut = count on success.
+SIAMESE_EXPORT SiameseResult sgpu_frames_deliver_recovery(unsigned count, const SgpuRecoveryPacket* packets,
+                                                          const unsigned* flows, void* deviceDst, size_t stride,
+                                                          unsigned* deviceLens, unsigned* queuedOut);
+/// Queue originals firstPacketNum .. firstPacketNum+count-1 held by `encoder`
+/// into caller-owned device rows, framed as SGPU_FRAME_ORIGINAL for `flow`
+/// (SGPU_FRAME_NONE: bare payloads): what a sender retransmitting a NACKed
+/// range needs, without a copy of its own of every original.
+/// Absent originals (never added, or already removed from the window by
+/// sgpu_encoder_remove_before): results[k] = Siamese_NeedMoreData,
+/// deviceLens[k] = 0 is written and the row is left untouched, as in
+/// sgpu_decoder_deliver_range -- an untouched row may still hold an older
+/// frame, so the lengths decide which rows to send.  Present ones: results[k] =
+/// Siamese_Success.  The call returns Siamese_Success even when some are
+/// absent; *queuedOut = the number present.
+/// Also Siamese_InvalidInput: a null encoder; firstPacketNum >
+/// SIAMESE_PACKET_NUM_MAX.  A disabled encoder returns Siamese_Disabled.
+SIAMESE_EXPORT SiameseResult sgpu_encoder_deliver_range(SgpuEncoder encoder, unsigned firstPacketNum, unsigned count,
+                                                        unsigned flow, void* deviceDst, size_t stride,
+                                                        unsigned* deviceLens,
+                                                        SiameseResult* results /* host, optional */,
+                                                        unsigned* queuedOut);
+
 /// Device timing of flushed work since the last reset (milliseconds).
 SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* totalMs);
 /// Device milliseconds per kernel class since the last sgpu_timing reset,
 /// while timing is enabled: [0] k_ingest, [1] k_exec, [2] k_ldpc, [3] the
 /// solve kernels (k_solve_pre + k_solve_tr + k_solve_main on launches of
 /// >= 16 solves, k_solve_main alone below that), [4] k_ge (sgpu_decode_device),
-/// [5] k_deliver (sgpu_decoder_deliver_range); count entries at most.
+/// [5] k_deliver (sgpu_decoder_deliver_range), [6] k_frame
+/// (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range); count entries
+/// at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -357,8 +432,9 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// (the host repeated the elimination), then the chained jobs whose decode
 /// carried gated wide-row picks (k_ldpc items), then [21] the delivery items
 /// queued (sgpu_decoder_deliver_range: one per packet of each range, absent
-/// ones included, counted when their submission is laid out); count entries
-/// at most.
+/// ones included, counted when their submission is laid out), then [22] the
+/// frame items queued likewise (sgpu_frames_deliver_recovery,
+/// sgpu_encoder_deliver_range); count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

@@ -140,6 +140,11 @@ void be_join_ge();
 /// in bytes, saturated to 32 bits (sizes the grid).  The caller queues it
 /// after every launch that writes the symbols (and after be_join_ge()).
 void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStride);
+/// A sender's packets framed into caller-owned rows (ops.h FrameItem), the
+/// grid and maxStride as be_launch_deliver's: each row gets its literal
+/// header, the packet and a zero tail, and its length word (zero, and an
+/// untouched row, for an absent packet).  Queued beside be_launch_deliver.
+void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t maxStride);
 
 /// Block until all queued work has finished.  Returns false on a device fault.
 bool be_sync();
@@ -178,7 +183,7 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-enum BeKernel { kBeIngest, kBeExec, kBeLdpc, kBeSolve, kBeGe, kBeDeliver, kBeKernelKinds };
+enum BeKernel { kBeIngest, kBeExec, kBeLdpc, kBeSolve, kBeGe, kBeDeliver, kBeFrame, kBeKernelKinds };
 void be_timing_enable(bool on);
 /// Device milliseconds of one kernel class since the last reset.
 double be_timing_kernel_ms(BeKernel kind);

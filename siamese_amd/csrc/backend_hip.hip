@@ -19,6 +19,8 @@
 //   k_ge           a decode's recovery matrix and its elimination (opt-in)
 //   k_deliver      decoded packets into caller-owned rows at a fixed stride,
 //                  lengths beside them (k_ingest backwards, opt-in)
+//   k_frame        a sender's originals and recovery packets as wire frames
+//                  into caller-owned rows (header, packet, zero tail; opt-in)
 //
 // GF(256) multiply by a wave-uniform constant uses three v_perm_b32 byte
 // lookups per dword (bits 0-2, 3-5, 6-7 of each byte) and one v_bitop3_b32
@@ -3795,6 +3797,98 @@ __global__ __launch_bounds__(64 * kDeliverWaves) void k_deliver(const DeliverIte
 }
 
 // ---------------------------------------------------------------------------
+// Framing (k_frame, ops.h FrameItem)
+//
+// k_deliver's shape for the sender's packets: one wave per (item, 8 KiB chunk
+// of its row), lane L of each 1 KiB tile writes row bytes [16L, 16L+16) with
+// one 16-byte store.  Nothing is parsed on the device: the host knows every
+// length, so the row's content is T = hdrLen + bytes, a literal header of up
+// to 11 bytes and then the packet from src, which has any byte alignment.
+// The source byte that lines up with row byte 0 is src - hdrLen; its low four
+// bits give a word offset and a byte shift that are uniform per item, so a
+// lane's 16 bytes come from the two aligned source words around them, loaded
+// (coalesced) and recombined with v_alignbyte_b32 under a uniform branch, as
+// in k_ingest.  An aligned word is loaded only if it holds a byte of
+// [src, src + bytes) (the second word of the first lane always does when the
+// first lies before src: hdrLen < 16).  The header bytes are merged into
+// lane 0 of tile 0, bytes at and past T are masked to zero and the zero fill
+// runs to the row's end; positions are 64-bit.  Two tiles' loads are in
+// flight before their stores.  No LDS, no atomics.
+
+__global__ __launch_bounds__(64 * kDeliverWaves) void k_frame(const FrameItem* __restrict__ items, uint32_t count)
+{
+    const uint32_t ii = __builtin_amdgcn_readfirstlane(blockIdx.x * kDeliverWaves + (threadIdx.x >> 6));
+    if (ii >= count)
+        return;
+    const uint32_t lane = threadIdx.x & 63;
+    const FrameItem it = items[ii];
+    const uint64_t stride = (uint64_t)it.stride16 << 4;
+    const uint32_t hl = it.hdrLen;
+    const uint64_t total = it.src != 0 ? (uint64_t)hl + it.bytes : 0;   // (<= stride: the host checked)
+    if (blockIdx.y == 0 && lane == 0)
+        *reinterpret_cast<GMEM uint32_t*>(it.lenOut) = (uint32_t)total;
+    if (it.src == 0)   // an absent packet: its row stays as it is
+        return;
+    // source address that lines up with row byte 0
+    const uint64_t base = it.src - hl;
+    const unsigned sh = (unsigned)(base & 15u);
+    const unsigned q = sh >> 2, r = sh & 3;
+    const uint64_t srcEnd = it.src + it.bytes;
+    const bool any = it.bytes != 0;
+    const uint32_t h0 = it.hdr[0] | (it.hdr[1] << 8) | (it.hdr[2] << 16) | ((uint32_t)it.hdr[3] << 24);
+    const uint32_t h1 = it.hdr[4] | (it.hdr[5] << 8) | (it.hdr[6] << 16) | ((uint32_t)it.hdr[7] << 24);
+    const uint32_t h2 = it.hdr[8] | (it.hdr[9] << 8) | (it.hdr[10] << 16);
+    const uint64_t step = (uint64_t)gridDim.y * kIngestChunkBytes;
+    for (uint64_t c0 = (uint64_t)blockIdx.y * kIngestChunkBytes; c0 < stride; c0 += step) {
+        const uint64_t c1 = c0 + kIngestChunkBytes < stride ? c0 + kIngestChunkBytes : stride;
+        for (uint64_t t = c0; t < c1; t += 2 * kTileBytes) {
+            uint4 out[2];
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                out[u] = make_uint4(0, 0, 0, 0);
+                if (p >= total)   // the zero fill: nothing to load
+                    continue;
+                const uint64_t a = (base + p) & ~(uint64_t)15;
+                const uint4 lo = (any && a < srcEnd && a + 16 > it.src) ? ld16(a) : make_uint4(0, 0, 0, 0);
+                const uint4 hi = (any && sh != 0 && a + 16 < srcEnd) ? ld16(a + 16) : make_uint4(0, 0, 0, 0);
+                const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                switch (q) {   // wave-uniform
+                case 0:
+                    out[u] = make_uint4(pick(w, 0, r, 0), pick(w, 0, r, 1), pick(w, 0, r, 2), pick(w, 0, r, 3));
+                    break;
+                case 1:
+                    out[u] = make_uint4(pick(w, 1, r, 0), pick(w, 1, r, 1), pick(w, 1, r, 2), pick(w, 1, r, 3));
+                    break;
+                case 2:
+                    out[u] = make_uint4(pick(w, 2, r, 0), pick(w, 2, r, 1), pick(w, 2, r, 2), pick(w, 2, r, 3));
+                    break;
+                default:
+                    out[u] = make_uint4(pick(w, 3, r, 0), pick(w, 3, r, 1), pick(w, 3, r, 2), pick(w, 3, r, 3));
+                    break;
+                }
+            }
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                if (p >= stride)
+                    continue;
+                uint4 v = out[u];
+                if (p == 0) {   // the frame header (at most 11 bytes) over source bytes
+                    const uint32_t m0 = byte_mask((int)hl), m1 = byte_mask((int)hl - 4), m2 = byte_mask((int)hl - 8);
+                    v.x = (v.x & ~m0) | (h0 & m0);
+                    v.y = (v.y & ~m1) | (h1 & m1);
+                    v.z = (v.z & ~m2) | (h2 & m2);
+                }
+                if (p + 16 > total)
+                    v = mask16(v, p < total ? (int)(total - p) : 0);
+                st16(it.dst + p, v);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 
 namespace {
@@ -4266,6 +4360,18 @@ void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStr
     const uint32_t chunks =
         std::min(kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxStride + kIngestChunkBytes - 1) / kIngestChunkBytes)));
     hipLaunchKernelGGL(k_deliver, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
+                       g_stream, items, count);
+}
+
+void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t maxStride)
+{
+    if (count == 0)
+        return;
+    Timed t(kBeFrame);
+    // (the grid of be_launch_deliver)
+    const uint32_t chunks =
+        std::min(kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxStride + kIngestChunkBytes - 1) / kIngestChunkBytes)));
+    hipLaunchKernelGGL(k_frame, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
                        g_stream, items, count);
 }
 

@@ -178,6 +178,75 @@ SIAMESE_EXPORT SiameseResult sgpu_encode_range(SgpuEncoder encoder, SgpuRecovery
     return r;
 }
 
+namespace {
+
+/// The row arguments the two framing calls share (siamese_gpu.h).
+bool frame_rows_ok(unsigned count, uint64_t dst, size_t stride, uint64_t lens)
+{
+    return !((!dst || !lens) && count) && (dst & 15u) == 0 && stride != 0 && (stride & 15u) == 0 &&
+           (uint64_t)stride <= (1ull << 32) && (lens & 3u) == 0;
+}
+
+} // namespace
+
+SIAMESE_EXPORT SiameseResult sgpu_encoder_deliver_range(SgpuEncoder encoder, unsigned firstPacketNum, unsigned count,
+                                                        unsigned flow, void* deviceDst, size_t stride,
+                                                        unsigned* deviceLens, SiameseResult* results,
+                                                        unsigned* queuedOut)
+{
+    if (queuedOut)
+        *queuedOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, lens = (uint64_t)(uintptr_t)deviceLens;
+    if (!encoder || !frame_rows_ok(count, dst, stride, lens) || (flow > kFrameMaxFlow && flow != SGPU_FRAME_NONE) ||
+        firstPacketNum > SIAMESE_PACKET_NUM_MAX)
+        return Siamese_InvalidInput;
+    static_assert(EncoderCore::kFrameNone == SGPU_FRAME_NONE, "SGPU_FRAME_NONE");
+    unsigned queued = 0;
+    const SiameseResult r = BE(encoder)->core.deliver_range(firstPacketNum, count, flow, dst, (uint64_t)stride, lens,
+                                                            results, &queued);
+    if (queuedOut)
+        *queuedOut = queued;
+    return r;
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_deliver_recovery(unsigned count, const SgpuRecoveryPacket* packets,
+                                                          const unsigned* flows, void* deviceDst, size_t stride,
+                                                          unsigned* deviceLens, unsigned* queuedOut)
+{
+    if (queuedOut)
+        *queuedOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, lens = (uint64_t)(uintptr_t)deviceLens;
+    if ((!packets && count) || !frame_rows_ok(count, dst, stride, lens))
+        return Siamese_InvalidInput;
+    // every packet is checked before any is queued
+    for (unsigned k = 0; k < count; ++k) {
+        const SgpuRecoveryPacket& p = packets[k];
+        // (DataBytes as sgpu_frames_send takes them)
+        if (!p.DeviceData || !p.Producer || p.DataBytes == 0 || p.DataBytes > SIAMESE_MAX_PACKET_BYTES ||
+            (flows && flows[k] > kFrameMaxFlow && flows[k] != SGPU_FRAME_NONE))
+            return Siamese_InvalidInput;
+        const bool framed = flows && flows[k] != SGPU_FRAME_NONE;
+        if ((uint64_t)(framed ? frame_header_bytes(kFrameRecovery, p.DataBytes) : 0) + p.DataBytes > stride)
+            return Siamese_InvalidInput;
+    }
+    if (!g_batchReady || Engine::global()->failed())
+        return Siamese_Disabled;
+    for (unsigned k = 0; k < count; ++k) {
+        const SgpuRecoveryPacket& p = packets[k];
+        uint8_t hdr[kFrameMaxHeader] = {};
+        unsigned h = 0;
+        if (flows && flows[k] != SGPU_FRAME_NONE)
+            h = frame_write_header(kFrameRecovery, flows[k], 0, p.DataBytes, hdr);
+        // (on the producing encoder's program, as sgpu_decoder_add_recovery's copy)
+        reinterpret_cast<Program*>(p.Producer)->frame((uint64_t)(uintptr_t)p.DeviceData, p.DataBytes, hdr, h,
+                                                      dst + (uint64_t)k * stride, lens + (uint64_t)k * 4,
+                                                      (uint64_t)stride);
+    }
+    if (queuedOut)
+        *queuedOut = count;
+    return Siamese_Success;
+}
+
 SIAMESE_EXPORT SgpuDecoder sgpu_decoder_create(void)
 {
     if (!g_batchReady)
@@ -597,13 +666,13 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[22] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[23] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
                             s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide,
-                            s.delivers};
-    for (unsigned k = 0; k < count && k < 22; ++k)
+                            s.delivers,   s.frames};
+    for (unsigned k = 0; k < count && k < 23; ++k)
         out[k] = v[k];
 }
 

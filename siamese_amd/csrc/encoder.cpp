@@ -1,6 +1,7 @@
 // encoder.cpp -- see encoder.h.  Line citations are to the reference
 // SiameseEncoder.cpp unless stated otherwise.
 #include "encoder.h"
+#include "frames.h"
 
 #include <algorithm>
 #include <cstring>
@@ -402,6 +403,48 @@ SiameseResult EncoderCore::get(SiameseOriginalPacket& packet)
     packet.PacketNum = s.column;
     packet.Data = mirror_ ? s.host().data() + s.header : s.buf.ptr + s.header;
     packet.DataBytes = s.bytes - s.header;
+    return Siamese_Success;
+}
+
+SiameseResult EncoderCore::deliver_range(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst,
+                                         uint64_t stride, uint64_t lens, SiameseResult* results, unsigned* queued)
+{
+    *queued = 0;
+    if (dead())
+        return Siamese_Disabled;
+    const bool framed = flow != kFrameNone;
+    // the unacknowledged window, as get() and remove_before() see it
+    auto held = [&](unsigned column) -> const EncSlot* {
+        const unsigned e = column_to_element(column);
+        if (e >= count_ || e < firstUnremoved_)
+            return nullptr;
+        const EncSlot& s = slot(e);
+        return s.bytes != 0 && s.column == column ? &s : nullptr;
+    };
+    // every length is known here: nothing is queued when a packet cannot fit
+    for (unsigned k = 0; k < count; ++k)
+        if (const EncSlot* s = held(column_add(firstNum, k))) {
+            const unsigned n = s->bytes - s->header;
+            if ((uint64_t)(framed ? frame_header_bytes(kFrameOriginal, n) : 0) + n > stride)
+                return Siamese_InvalidInput;
+        }
+    for (unsigned k = 0; k < count; ++k) {
+        const unsigned column = column_add(firstNum, k);
+        const EncSlot* s = held(column);
+        uint8_t hdr[kFrameMaxHeader] = {};
+        unsigned h = 0, n = 0;
+        if (s) {
+            n = s->bytes - s->header;
+            if (framed)
+                h = frame_write_header(kFrameOriginal, flow, column, n, hdr);
+        }
+        prog_.frame(s ? s->buf.addr() + s->header : 0, n, hdr, h, dst + (uint64_t)k * stride,
+                    lens + (uint64_t)k * 4, stride);
+        if (results)
+            results[k] = s ? Siamese_Success : Siamese_NeedMoreData;
+        if (s)
+            ++*queued;
+    }
     return Siamese_Success;
 }
 

@@ -108,6 +108,20 @@ public:
                             unsigned count, unsigned* firstNum, unsigned* added);
     void remove_before(unsigned firstKeptColumn);
     SiameseResult get(SiameseOriginalPacket& packet);
+    /// sgpu_encoder_deliver_range: queue the framing of originals firstNum,
+    /// firstNum + 1, ... into the caller's device rows dst + k * stride, their
+    /// lengths into the uint32 words at lens + 4 k (Program::frame, one item
+    /// per packet).  Source and length come from the slot (buf + header,
+    /// bytes - header); flow <= kFrameMaxFlow: a kFrameOriginal header
+    /// (frame_write_header) goes before the payload, kFrameNone: none.  A packet
+    /// outside the unacknowledged window (never added, or removed) is absent:
+    /// its item writes only a zero length.  Never waits.  results[k]
+    /// (optional) = Success / NeedMoreData, *queued = packets present.
+    /// InvalidInput, with nothing queued, when header + payload of a present
+    /// packet exceed the stride.
+    static constexpr unsigned kFrameNone = 0xffffffffu;
+    SiameseResult deliver_range(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst, uint64_t stride,
+                                uint64_t lens, SiameseResult* results, unsigned* queued);
     /// Generate the next recovery packet (device ops queued, not flushed).
     SiameseResult encode(EncodeOut& out);
     /// `count` encode() calls in one (sgpu_encode_range): out[k] as the k-th

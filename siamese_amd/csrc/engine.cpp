@@ -52,6 +52,7 @@ void EngineStats::add(const EngineStats& o)
     geRetried += o.geRetried;
     geChainedWide += o.geChainedWide;
     delivers += o.delivers;
+    frames += o.frames;
 }
 
 namespace {
@@ -115,6 +116,7 @@ void ProgramBody::clear()
     copies.clear();
     lcb.clear();
     ndeliver = 0;   // (the items' vector keeps its elements: not touched here)
+    nframe = 0;
     gateOpen = false;
 }
 
@@ -885,6 +887,25 @@ void Program::deliver(uint64_t src, uint32_t cap, uint64_t dst, uint64_t lenOut,
     b_->delivers[b_->ndeliver++] = it;
 }
 
+void Program::frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t hdrLen, uint64_t dst,
+                    uint64_t lenOut, uint64_t stride)
+{
+    touch();
+    FrameItem it;
+    it.src = src;
+    it.dst = dst;
+    it.lenOut = lenOut;
+    it.bytes = bytes;
+    it.stride16 = (uint32_t)(stride >> 4);
+    std::memset(it.hdr, 0, sizeof(it.hdr));
+    std::memcpy(it.hdr, hdr, hdrLen);
+    it.hdrLen = (uint8_t)hdrLen;
+    it.pad = 0;
+    if (b_->nframe == b_->frames.size())
+        b_->frames.emplace_back();
+    b_->frames[b_->nframe++] = it;
+}
+
 // ---------------------------------------------------------------------------
 // Shard queues
 
@@ -1431,6 +1452,8 @@ struct Batch
     bool geChained = false;                 // a job writes into the upload (kGeChained)
     size_t oDeliver = 0, nDeliver = 0;     // delivery items of every body (ops.h DeliverItem)
     uint32_t maxDeliverStride = 0;         // ... their longest row in bytes, saturated (k_deliver's grid)
+    size_t oFrame = 0, nFrame = 0;         // frame items of every body (ops.h FrameItem)
+    uint32_t maxFrameStride = 0;           // ... their longest row, as maxDeliverStride (k_frame's grid)
     size_t oCopy = 0;                      // the download copy list (BeCopy records)
     uint64_t wideBase = 0;                 // this submission's k_ldpc scratch: bytes into the ring
     bool wideGated = false;                // k_ldpc items of gated ops: the launches take the gate
@@ -2173,10 +2196,12 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     std::vector<GeRef> grefs;
     size_t geInBytes = 0;
     size_t nDeliver = 0;   // delivery items of every body
+    size_t nFrame = 0;     // frame items of every body
     for (int g = 0; g < 2; ++g)
         for (size_t pi = 0; pi < bt.bodies[g].size(); ++pi) {
             const ProgramBody* p = bt.bodies[g][pi];
             nDeliver += p->ndeliver;   // (beside nges: no line of the body this pass does not read anyway)
+            nFrame += p->nframe;
             for (size_t k = 0; k < p->nges; ++k) {
                 const ProgramBody::PendingGe& ge = p->ges[k];
                 GeDesc d;
@@ -2211,6 +2236,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
         }
     bt.nGe = gdescs.size();
     bt.nDeliver = nDeliver;
+    bt.nFrame = nFrame;
 
     constexpr size_t kIngestChunk = SGPU_INGEST_CHUNK;
     size_t nIngest = 0, stageBytes = 0, nIngBlocks = 0;
@@ -2275,6 +2301,9 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     // all after the last phase: launch_batch)
     bt.oDeliver = off;
     off = align16(off + nDeliver * sizeof(DeliverItem));
+    // the frame items, likewise (one k_frame launch beside k_deliver's)
+    bt.oFrame = off;
+    off = align16(off + nFrame * sizeof(FrameItem));
     // the download copy list (the counters and results, then every range)
     size_t nDownloads = 0;
     for (const Shard::Queues& q : bt.queues)
@@ -2483,6 +2512,20 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
             }
         bt.maxDeliverStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
     }
+    if (nFrame) {
+        FrameItem* fi = (FrameItem*)(up + bt.oFrame);
+        uint32_t max16 = 0;
+        for (int g = 0; g < 2; ++g)
+            for (const ProgramBody* p : bt.bodies[g]) {
+                if (p->nframe == 0)
+                    continue;
+                std::memcpy(fi, p->frames.data(), p->nframe * sizeof(FrameItem));
+                for (uint32_t k = 0; k < p->nframe; ++k)
+                    max16 = std::max(max16, fi[k].stride16);
+                fi += p->nframe;
+            }
+        bt.maxFrameStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
+    }
 
     // download area: the byte counters (kAcctBytes), the solve results, then
     // each requested range
@@ -2513,8 +2556,10 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     }
 
     st.flushes = 1;
-    st.launches = phases.size() + (nIngest ? 1 : 0) + (gdescs.empty() ? 0 : 1) + (nDeliver ? 1 : 0);
+    st.launches = phases.size() + (nIngest ? 1 : 0) + (gdescs.empty() ? 0 : 1) + (nDeliver ? 1 : 0) +
+                  (nFrame ? 1 : 0);
     st.delivers = nDeliver;
+    st.frames = nFrame;
     st.ops = nOps;
     st.terms = nTerms;
     st.solves = sdescs.size();
@@ -2632,6 +2677,12 @@ void Engine::launch_batch(Batch& bt)
     // (released buffers return to the arena in reclaim_batch, after the fence).
     if (bt.nDeliver)
         be_launch_deliver((const DeliverItem*)(bt.upBase + bt.oDeliver), (uint32_t)bt.nDeliver, bt.maxDeliverStride);
+    // ... and its frames, on the same terms: a recovery packet encoded in this
+    // submission has its final bytes, an original added in it was ingested by
+    // the first launch, and a recovery buffer the encoder's next encode of
+    // this submission released is still untouched
+    if (bt.nFrame)
+        be_launch_frame((const FrameItem*)(bt.upBase + bt.oFrame), (uint32_t)bt.nFrame, bt.maxFrameStride);
     // the counters and solve results, then the downloads, in one call (one
     // kernel when small; its range list was laid out with the upload: a
     // drop-in submission carries a range per application call)

@@ -310,6 +310,7 @@ struct ProgramBody
     // items in `delivers` (below), beside the counts every submission reads:
     // a body without deliveries costs detach and assembly no cache line more
     uint32_t ndeliver = 0;
+    uint32_t nframe = 0;   // items in `frames` (below), kept here for the same reason
     std::vector<Completion> callbacks;
     // objects the callbacks use, kept alive until they have run (so a
     // callback captures a raw pointer and fits std::function's inline
@@ -348,6 +349,10 @@ struct ProgramBody
     /// independent of the segments, run by the submission's one k_deliver
     /// launch after all of them.  ndeliver in use (capacity is kept).
     std::vector<DeliverItem> delivers;
+    /// A sender's packets to frame into the caller's device rows (ops.h
+    /// FrameItem), run by the submission's one k_frame launch beside
+    /// k_deliver's.  nframe in use (capacity is kept).
+    std::vector<FrameItem> frames;
     void lc_seal();                     // seals the open OP_LINCOMBS batch
     /// Move the segment's last op (an OP_LINCOMB) into the open batch, or
     /// seal the batch first when they are not independent.
@@ -357,7 +362,7 @@ struct ProgramBody
 
     bool empty() const
     {
-        return nges == 0 && ndeliver == 0 &&
+        return nges == 0 && ndeliver == 0 && nframe == 0 &&
                (nsegs == 0 ||
                 (nsegs == 1 && segs[0].ops.empty() && copies.empty() && lcb.items.empty() && !rb.open));
     }
@@ -518,6 +523,16 @@ public:
     /// it.  A program whose only work is delivery still makes a submission.
     void deliver(uint64_t src, uint32_t cap, uint64_t dst, uint64_t lenOut, uint64_t stride);
 
+    /// Queue a frame item (ops.h FrameItem): hdrLen (<= kFrameMaxHeader)
+    /// literal header bytes, then `bytes` from src (any alignment; 0: an absent
+    /// packet) into the caller's row dst[0, stride), hdrLen + bytes <= stride,
+    /// the sum at lenOut.  Ordered as deliver()'s items: one launch after the
+    /// submission's last executor / solve launch, so a recovery packet encoded
+    /// in the same submission is framed from its final bytes.  A program whose
+    /// only work is framing still makes a submission.
+    void frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t hdrLen, uint64_t dst, uint64_t lenOut,
+               uint64_t stride);
+
     bool empty() const { return !b_ || b_->empty(); }
 
 private:
@@ -561,6 +576,7 @@ struct EngineStats
     uint64_t geJobs = 0, geChained = 0, geRetried = 0;
     uint64_t geChainedWide = 0;   // chained jobs whose decode carried gated k_ldpc items (wide rows)
     uint64_t delivers = 0;        // delivery items queued (sgpu_decoder_deliver_range)
+    uint64_t frames = 0;          // frame items queued (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range)
 
     void add(const EngineStats& o);
 };

@@ -415,6 +415,33 @@ static_assert(sizeof(DeliverItem) == 32, "DeliverItem layout");
 constexpr uint32_t kDeliverWaves = 4;
 constexpr uint32_t kDeliverMaxChunks = 4096;
 
+/// One sender packet framed into a caller-owned device row (k_frame,
+/// sgpu_frames_deliver_recovery / sgpu_encoder_deliver_range).  With
+/// T = hdrLen + bytes:  dst[0, hdrLen) = hdr, dst[hdrLen, T) = src[0, bytes),
+/// dst[T, stride) = 0 and *lenOut = T (the host guarantees T <= stride).  src
+/// has any byte alignment (a recovery packet's arena buffer, or an original's
+/// slot address plus its prefix bytes); src = 0: an absent packet, only
+/// *lenOut = 0 is written.  Only aligned 16-byte words holding a byte of
+/// [src, src + bytes) are read, nothing outside [dst, dst + stride) and the
+/// length word is written.  hdr is the literal frame header (frames.h: an
+/// original's is prefix <= 4 plus 7 bytes), hdrLen = 0 for a bare packet.  The
+/// launch runs after every other launch of its submission, beside k_deliver.
+constexpr unsigned kFrameMaxHeader = 11;
+struct FrameItem
+{
+    uint64_t src;        // the packet's first byte (0: absent)
+    uint64_t dst;        // the row, 16-byte aligned
+    uint64_t lenOut;     // uint32 length word, 4-byte aligned
+    uint32_t bytes;      // packet bytes after the header
+    uint32_t stride16;   // the row's bytes / 16 (1 .. 2^28)
+    uint8_t hdr[kFrameMaxHeader];
+    uint8_t hdrLen;
+    uint32_t pad;
+};
+static_assert(sizeof(FrameItem) == 48, "FrameItem layout");
+/// k_frame's grid is k_deliver's: kDeliverWaves items per workgroup, at most
+/// kDeliverMaxChunks chunk rows.
+
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)
 /// Solves with more rows than this stage 256-byte tiles (16 lanes x 16 bytes

@@ -475,6 +475,26 @@ void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t)
     }
 }
 
+// k_frame (ops.h FrameItem): the literal header, the packet and a zero tail
+// into the row, the sum of the first two in the length word; an absent packet
+// only its zero length word.
+void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t)
+{
+    if (noexec())
+        return;
+    for (uint32_t i = 0; i < count; ++i) {
+        const FrameItem& it = items[i];
+        const uint64_t stride = (uint64_t)it.stride16 << 4;
+        const uint64_t total = it.src != 0 ? (uint64_t)it.hdrLen + it.bytes : 0;
+        const uint32_t lw = (uint32_t)total;
+        std::memcpy(P(it.lenOut), &lw, 4);
+        if (it.src == 0)
+            continue;
+        for (uint64_t b = 0; b < stride; ++b)
+            P(it.dst)[b] = b < it.hdrLen ? it.hdr[b] : b < total ? P(it.src)[b - it.hdrLen] : 0;
+    }
+}
+
 static void solve_prefix(const SolveDesc* solves, const SolveRow* rows, const uint8_t* coef,
                             uint32_t* results, uint32_t count, uint64_t* acct)
 {
