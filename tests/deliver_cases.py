@@ -41,10 +41,14 @@ def load(path, device=-1):
     L.sgpu_h2d.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.sgpu_gather.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgpu_encoder_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
+    L.sgpu_encoder_add_range.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint,
+                                         C.c_void_p, C.c_void_p]
     L.sgpu_encode_range.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
     L.sgpu_encoder_free.argtypes = [C.c_void_p]
     L.sgpu_decoder_free.argtypes = [C.c_void_p]
     L.sgpu_decoder_add_original.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint]
+    L.sgpu_decoder_add_original_range.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint,
+                                                  C.c_uint, C.c_void_p, C.c_void_p]
     L.sgpu_decoder_add_recovery.argtypes = [C.c_void_p, C.c_void_p]
     L.sgpu_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgpu_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -129,40 +133,76 @@ def check_row(row, length, data, what):
 
 class Stream:
     """Originals in device memory at odd addresses; a decoder that received
-    all but `lost`, and (with recovery > 0) an encoder's recovery packets."""
+    all but `lost`, and (with recovery > 0) an encoder's recovery packets.
 
-    def __init__(self, L, lengths, lost=(), recovery=0, seed=1, pitch=None):
+    data: the payloads themselves (default: payload(seed * 1000 + i, n)).
+    offsets: original i at byte offsets[i] of its pitch slot (default: 3 for
+    all).  ranges: the encoder takes the originals by one
+    sgpu_encoder_add_range call and the decoder each unbroken stretch of
+    received ones by one sgpu_decoder_add_original_range call, both with a
+    bytes[] array."""
+
+    def __init__(self, L, lengths, lost=(), recovery=0, seed=1, pitch=None, data=None, offsets=None, ranges=False):
         self.L = L
-        self.data = [payload(seed * 1000 + i, n) for i, n in enumerate(lengths)]
+        self.data = data or [payload(seed * 1000 + i, n) for i, n in enumerate(lengths)]
+        assert [len(d) for d in self.data] == list(lengths)
+        count = len(lengths)
+        self.offsets = offsets or [3] * count
+        assert not (ranges and offsets), "a range has one stride"
         # (an even pitch that is no multiple of 16 and an odd first offset:
         # every source address is odd, their low four bits differ)
         self.pitch = pitch or ((max(lengths) + 34) & ~15) + 2
-        blob = bytearray(3 + self.pitch * len(lengths))
+        assert all(o + n <= self.pitch for o, n in zip(self.offsets, lengths))
+        blob = bytearray(max(self.offsets) + self.pitch * count)
         for i, d in enumerate(self.data):
-            blob[3 + i * self.pitch:3 + i * self.pitch + len(d)] = d
+            o = self.offsets[i] + i * self.pitch
+            blob[o:o + len(d)] = d
         self.src = L.sgpu_device_alloc(len(blob))
         assert self.src and L.sgpu_h2d(self.src, bytes(blob), len(blob)) == 0
+        lens = (C.c_uint * count)(*lengths)
         self.enc = None
         self.recs = None
         if recovery:
             self.enc = L.sgpu_encoder_create()
-            for i, d in enumerate(self.data):
-                num = C.c_uint(0)
-                assert L.sgpu_encoder_add(self.enc, self.at(i), len(d), C.byref(num)) == SUCCESS and num.value == i
+            if ranges:
+                first, added = C.c_uint(99), C.c_uint(0)
+                assert L.sgpu_encoder_add_range(self.enc, self.at(0), self.pitch, lens, 0, count, C.byref(first),
+                                                C.byref(added)) == SUCCESS
+                assert (first.value, added.value) == (0, count)
+            else:
+                for i, d in enumerate(self.data):
+                    num = C.c_uint(0)
+                    assert L.sgpu_encoder_add(self.enc, self.at(i), len(d), C.byref(num)) == SUCCESS
+                    assert num.value == i
             self.recs = (Rec * recovery)()
             made = C.c_uint(0)
             assert L.sgpu_encode_range(self.enc, self.recs, recovery, C.byref(made)) == SUCCESS
             assert made.value == recovery
         self.dec = L.sgpu_decoder_create()
         assert self.dec
-        for i, d in enumerate(self.data):
-            if i not in lost:
-                assert L.sgpu_decoder_add_original(self.dec, i, self.at(i), len(d)) == SUCCESS
+        if ranges:
+            i = 0
+            while i < count:
+                j = i
+                while j < count and j not in lost:
+                    j += 1
+                if j > i:
+                    res = (C.c_int * (j - i))(*([-1] * (j - i)))
+                    calls = C.c_uint(0)
+                    assert L.sgpu_decoder_add_original_range(
+                        self.dec, i, self.at(i), self.pitch, C.byref(lens, 4 * i), 0, j - i, res,
+                        C.byref(calls)) == SUCCESS
+                    assert calls.value == j - i and list(res) == [SUCCESS] * (j - i)
+                i = j + 1
+        else:
+            for i, d in enumerate(self.data):
+                if i not in lost:
+                    assert L.sgpu_decoder_add_original(self.dec, i, self.at(i), len(d)) == SUCCESS
         for k in range(recovery):
             assert L.sgpu_decoder_add_recovery(self.dec, C.byref(self.recs[k])) == SUCCESS
 
     def at(self, i):
-        return self.src + 3 + i * self.pitch
+        return self.src + self.offsets[i] + i * self.pitch
 
     def decode(self, device=False):
         out = C.c_void_p()
