@@ -350,7 +350,9 @@ SIAMESE_EXPORT long long sgpu_frames_send(unsigned count, const SgpuRecoveryPack
     h+n (uint32, device memory).  Rows are multiples of 16 bytes with zero
     tails, so the whole buffer read as one byte string is a valid frame stream
     for sgpu_frames_parse / sgpu_frames_recv: ready for one copy to the host,
-    for a NIC that reads device memory, or for a decoder on the same GPU.
+    for a NIC that reads device memory, or for a decoder on the same GPU
+    (sgpu_frames_scan_rows + sgpu_frames_recv_rows below take the rows where
+    they lie).
 
     Neither call ever waits for the GPU: rows and lengths are in place when
     the submission that carries the call completes (sgpu_flush / sgpu_wait /
@@ -407,6 +409,105 @@ SIAMESE_EXPORT SiameseResult sgpu_encoder_deliver_range(SgpuEncoder encoder, uns
                                                         SiameseResult* results /* host, optional */,
                                                         unsigned* queuedOut);
 
+/*
+    Frame rows that exist only in device memory, into decoders: the way in
+    that matches the two calls above (and a NIC that writes datagrams into
+    HBM).  sgpu_frames_recv needs an identical host copy of the whole frame
+    stream; here the host gets 32 bytes per row and the payloads never leave
+    the device.  sgpu_frames_scan_rows has the device read each row's frame
+    header, and for a recovery packet its first and last bytes, into one
+    SgpuRowHead; sgpu_frames_recv_rows routes the rows to their decoders from
+    those records:
+
+        ticket = sgpu_frames_scan_rows(rows, stride, lens, count, heads);
+        sgpu_gather_wait(ticket);
+        sgpu_frames_recv_rows(decoders, n, heads, rows, stride, count, results, &accepted);
+
+    Row k starts at deviceRows + k*stride and holds one frame from its first
+    byte (the row contract of the deliver calls above, or any datagram of the
+    "Framed datagrams" format), rows 16-byte aligned, stride a multiple of 16.
+*/
+#define SGPU_ROW_EMPTY     0   /* no frame in the row */
+#define SGPU_ROW_OK        1
+#define SGPU_ROW_MALFORMED 2
+
+/// One row's record: 32 bytes, every field little-endian as the host reads
+/// it, records 16-byte aligned in pinnedOut.  An empty or malformed row's
+/// record is zero but for Status.
+typedef struct SgpuRowHead
+{
+    unsigned      FrameBytes;  ///< header + data bytes of the frame in this row (its prefix + L); 0: empty or malformed row
+    unsigned char Status;      ///< SGPU_ROW_OK / SGPU_ROW_EMPTY / SGPU_ROW_MALFORMED
+    unsigned char Type;        ///< SGPU_FRAME_ORIGINAL / SGPU_FRAME_RECOVERY
+    unsigned char HeaderBytes; ///< offset of the data in the row (<= 11)
+    unsigned char TailBytes;   ///< valid bytes in Tail: min(8, DataBytes); originals: 0
+    unsigned      Flow;
+    unsigned      PacketNum;   ///< originals (recovery packets: 0)
+    unsigned      DataBytes;
+    unsigned char Head[4];     ///< recovery: first min(4, DataBytes) bytes of the packet, rest zero
+    unsigned char Tail[8];     ///< recovery: the packet's last TailBytes bytes, right-aligned, rest zero
+} SgpuRowHead;
+#if defined(__cplusplus)
+static_assert(sizeof(SgpuRowHead) == 32, "SgpuRowHead is 32 bytes");
+#else
+_Static_assert(sizeof(SgpuRowHead) == 32, "SgpuRowHead is 32 bytes");
+#endif
+
+/// Scan `count` frame rows into pinnedOut[0, count) (pinned host memory,
+/// sgpu_host_alloc) with one kernel launch.  A gather, with the contract of
+/// sgpu_gather_async and sgpu_frames_send: never waits, returns a gather
+/// ticket (> 0) for sgpu_gather_wait, may run beside instance calls;
+/// pinnedOut[k] is valid once sgpu_gather_wait(ticket) returns 0.  The rows
+/// were written by COMPLETED submissions or by something outside the library;
+/// they are read before the device work of any later submission runs.
+///
+/// deviceLens (optional, uint32 in device memory, as the deliver calls write
+/// them): deviceLens[k] == 0 makes row k empty whatever bytes it still holds
+/// (the lengths decide); a non-zero length must equal the frame's own
+/// prefix + L, or the row is malformed.  deviceLens == NULL: a zero first byte
+/// is an empty row, otherwise the frame's own length prefix decides.
+/// A row is malformed when: its length prefix gives L = 0 or prefix + L >
+/// stride (the prefix is judged exactly as sgpu_frames_parse judges it, which
+/// accepts a prefix wider than its L needs); type > 1; L is not larger than
+/// the type's inner header (4 bytes, an original's 7); an original's
+/// PacketNum > SIAMESE_PACKET_NUM_MAX; DataBytes > SIAMESE_MAX_PACKET_BYTES.
+/// Each row stands alone: a malformed row never stops the scan.
+///
+/// Returns -1, with nothing queued: null deviceRows or pinnedOut with
+/// count > 0; deviceRows not 16-byte aligned; stride zero, not a multiple of
+/// 16 or above 4 GiB; deviceLens not 4-byte aligned; pinnedOut not 16-byte
+/// aligned; a failed device.  count == 0 returns a valid ticket that is
+/// already complete.
+SIAMESE_EXPORT long long sgpu_frames_scan_rows(const void* deviceRows, size_t stride, const unsigned* deviceLens,
+                                               unsigned count, SgpuRowHead* pinnedOut);
+/// Host only: hand the rows to their decoders from their records, queueing
+/// work like sgpu_frames_recv and waiting for nothing.  For row k with Status
+/// OK, the data at deviceRows + k*stride + HeaderBytes goes to decoders[Flow]:
+/// an original to sgpu_decoder_add_original, a recovery packet to
+/// sgpu_decoder_add_recovery (its footer parsed from Tail, its head taken from
+/// Head; the bytes are copied from the row by the next submission).
+/// results[k] (optional) = that call's result; Siamese_InvalidInput for a flow
+/// without a decoder or a decoder with a device matrix job pending
+/// (sgpu_decode_device), as in sgpu_frames_recv.  Empty rows: results[k] =
+/// Siamese_NeedMoreData, skipped.  Malformed rows: Siamese_InvalidInput,
+/// skipped; the rows after them are still delivered.  The records are caller
+/// data and never trusted: one whose Status is unknown, whose HeaderBytes +
+/// DataBytes exceeds stride or FrameBytes, or whose Type, HeaderBytes,
+/// TailBytes, DataBytes, Flow or PacketNum the format cannot produce, counts as
+/// malformed.  *acceptedOut = the rows handed to a decoder.
+/// Returns Siamese_InvalidInput, with nothing queued, for a null acceptedOut
+/// and for null decoders, heads or deviceRows with count > 0, heads not
+/// 4-byte aligned, and the scan's rules for deviceRows and stride; otherwise
+/// the first per-row result that is neither Success nor NeedMoreData (Success
+/// if none).  For well-formed rows the decoders end in the state
+/// sgpu_frames_recv leaves them in when given a host copy of the same bytes.
+/// The decoders must not be driven concurrently with this call; the rows stay
+/// untouched until the next submission has completed.
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_rows(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                   const SgpuRowHead* heads, const void* deviceRows, size_t stride,
+                                                   unsigned count, SiameseResult* results /* optional */,
+                                                   unsigned* acceptedOut);
+
 /// Device timing of flushed work since the last reset (milliseconds).
 SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* totalMs);
 /// Device milliseconds per kernel class since the last sgpu_timing reset,
@@ -414,8 +515,9 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// solve kernels (k_solve_pre + k_solve_tr + k_solve_main on launches of
 /// >= 16 solves, k_solve_main alone below that), [4] k_ge (sgpu_decode_device),
 /// [5] k_deliver (sgpu_decoder_deliver_range), [6] k_frame
-/// (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range); count entries
-/// at most.
+/// (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range), [7] k_scan
+/// (sgpu_frames_scan_rows: launched on the gather stream, counted once its
+/// gather has been waited for); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -434,7 +536,9 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// queued (sgpu_decoder_deliver_range: one per packet of each range, absent
 /// ones included, counted when their submission is laid out), then [22] the
 /// frame items queued likewise (sgpu_frames_deliver_recovery,
-/// sgpu_encoder_deliver_range); count entries at most.
+/// sgpu_encoder_deliver_range), then [23] the rows scanned
+/// (sgpu_frames_scan_rows, counted when the scan is queued); count entries at
+/// most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

@@ -22,6 +22,30 @@ class RecoveryPacket(ctypes.Structure):
     _fields_ = [("DataBytes", ctypes.c_uint), ("Data", ctypes.POINTER(ctypes.c_ubyte))]
 
 
+class RowHead(ctypes.Structure):
+    """SgpuRowHead (siamese_gpu.h): one frame row's record, 32 bytes."""
+    _fields_ = [("FrameBytes", ctypes.c_uint), ("Status", ctypes.c_ubyte), ("Type", ctypes.c_ubyte),
+                ("HeaderBytes", ctypes.c_ubyte), ("TailBytes", ctypes.c_ubyte), ("Flow", ctypes.c_uint),
+                ("PacketNum", ctypes.c_uint), ("DataBytes", ctypes.c_uint), ("Head", ctypes.c_ubyte * 4),
+                ("Tail", ctypes.c_ubyte * 8)]
+
+
+ROW_EMPTY, ROW_OK, ROW_MALFORMED = 0, 1, 2
+
+
+def bind_rows_abi(L):
+    """Prototypes of the siamese_gpu.h calls that take frame rows where they
+    lie in device memory, on a ctypes library that exports the batch ABI."""
+    vp, u = ctypes.c_void_p, ctypes.c_uint
+    L.sgpu_frames_scan_rows.restype = ctypes.c_longlong
+    L.sgpu_frames_scan_rows.argtypes = [vp, ctypes.c_size_t, vp, u, vp]
+    L.sgpu_frames_recv_rows.restype = ctypes.c_int
+    L.sgpu_frames_recv_rows.argtypes = [vp, u, vp, vp, ctypes.c_size_t, u, vp, vp]
+    L.sgpu_gather_wait.restype = ctypes.c_int
+    L.sgpu_gather_wait.argtypes = [ctypes.c_longlong]
+    return L
+
+
 class SiameseError(RuntimeError):
     def __init__(self, what, code):
         name = RESULT_NAMES[code] if 0 <= code < 6 else str(code)

@@ -176,6 +176,14 @@ void be_mark_release(void* mark);
 /// hostOut holds the bytes (be_mark_sync).  False if it could not be queued.
 bool be_gather(const IngestDesc* descsHost, void* descsDev, uint32_t count, const void* devStage,
                void* hostOut, size_t bytes, void** packed, void** landed);
+/// One k_scan launch on the gather stream (ops.h RowHead): one record per
+/// row of rows + k * stride, k < count, into devStage (count * 32 bytes,
+/// device memory), then one copy of the records to hostOut (pinned), without
+/// waiting.  lens: the rows' length words in device memory, or null.  The
+/// marks are be_gather's: *packed once the rows have been read, *landed once
+/// hostOut holds the records.  False if it could not be queued.
+bool be_scan_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, void* devStage,
+                  void* hostOut, void** packed, void** landed);
 /// Block until the device has passed `mark`, then recycle it; false on a
 /// device fault.
 bool be_mark_sync(void* mark);
@@ -183,7 +191,9 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-enum BeKernel { kBeIngest, kBeExec, kBeLdpc, kBeSolve, kBeGe, kBeDeliver, kBeFrame, kBeKernelKinds };
+/// (kBeScan is bracketed on the gather stream: be_sync waits for a bracket of
+/// that class still in flight before it folds it in)
+enum BeKernel { kBeIngest, kBeExec, kBeLdpc, kBeSolve, kBeGe, kBeDeliver, kBeFrame, kBeScan, kBeKernelKinds };
 void be_timing_enable(bool on);
 /// Device milliseconds of one kernel class since the last reset.
 double be_timing_kernel_ms(BeKernel kind);

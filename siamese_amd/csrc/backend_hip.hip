@@ -21,6 +21,8 @@
 //                  lengths beside them (k_ingest backwards, opt-in)
 //   k_frame        a sender's originals and recovery packets as wire frames
 //                  into caller-owned rows (header, packet, zero tail; opt-in)
+//   k_scan         frame rows in device memory into 32-byte host records
+//                  (header fields, a recovery packet's head and tail; opt-in)
 //
 // GF(256) multiply by a wave-uniform constant uses three v_perm_b32 byte
 // lookups per dword (bits 0-2, 3-5, 6-7 of each byte) and one v_bitop3_b32
@@ -3889,6 +3891,86 @@ __global__ __launch_bounds__(64 * kDeliverWaves) void k_frame(const FrameItem* _
 }
 
 // ---------------------------------------------------------------------------
+// Row scan (k_scan, ops.h RowHead)
+//
+// The way in for frame rows that exist only in device memory: one lane per
+// row reads the row's first aligned 16 bytes (the header is at most 11), and
+// everything the host needs of the row goes out as one 32-byte record, two
+// 16-byte stores per lane, 2 KiB contiguous per wave.  The prefix is parsed
+// as frames_parse parses it; the header after it is the 128-bit word shifted
+// down by the prefix bytes, so type, flow and PacketNum (or a recovery
+// packet's first four bytes) are fixed bit fields of one 64-bit value.  A
+// recovery row also gives its last min(8, dataBytes) bytes, which end
+// anywhere in the row: the one or two aligned words that hold them are loaded
+// (the first word again from its register) and recombined with 64-bit shifts
+// by the per-lane byte offset.  Both words lie inside the row, because the
+// frame ends at or before row + stride and the stride is a multiple of 16.
+// Adjacent lanes read addresses `stride` apart, so a wave's load is 64
+// requests to 64 different cache lines, not one 1 KiB burst: the kernel is
+// bound by request rate, not bytes, and what it buys is that a line or two
+// per row is fetched instead of the row.  One lane per row keeps 64
+// independent requests in flight per wave; a wave per row would fetch the same
+// lines with 63 idle lanes.  No LDS, no atomics.
+
+__device__ __forceinline__ uint64_t pack64(uint32_t lo, uint32_t hi)
+{
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_scan(uint64_t rows, uint64_t stride,
+                                                       const uint32_t* __restrict__ lens, uint32_t count,
+                                                       uint64_t out)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kScanThreads + threadIdx.x;
+    if (k >= count)
+        return;
+    const uint64_t row = rows + k * stride;
+    const uint32_t len = lens ? lens[k] : 0;
+    const uint4 f = ld16(row);
+    uint4 r0 = make_uint4(0, kRowEmpty, 0, 0), r1 = make_uint4(0, 0, 0, 0);
+    if (lens ? len != 0 : (f.x & 0xffu) != 0) {
+        r0.y = kRowMalformed;
+        uint32_t L = 0;
+        const uint32_t h = (uint32_t)parse_prefix(f.x, 4, &L);   // 1..4: four bytes are at hand
+        // row bytes [h, h + 8): type, flow, then PacketNum or the packet's first bytes
+        const uint64_t x = (pack64(f.x, f.y) >> (8u * h)) | (pack64(f.z, f.w) << (64u - 8u * h));
+        const uint32_t type = (uint32_t)x & 0xffu;
+        const uint32_t inner = type == 0 ? 7u : 4u;
+        const uint32_t flow = (uint32_t)(x >> 8) & 0xffffffu;
+        const uint32_t num = type == 0 ? (uint32_t)(x >> 32) & 0xffffffu : 0u;
+        const uint32_t total = h + L;   // (L < 2^29)
+        if (L >= 1 && (!lens || len == total) && type <= 1 && L > inner && total <= stride && num <= 0x3fffffu &&
+            L - inner <= 0x1fffffffu) {
+            const uint32_t D = L - inner;
+            uint32_t head = 0, T = 0;
+            uint64_t tail = 0;
+            if (type == 1) {
+                head = (uint32_t)(x >> 32) & byte_mask((int)D);
+                T = D < 8 ? D : 8;
+                const uint32_t s0 = total - T;   // the tail is row bytes [s0, total)
+                const uint32_t wlo = s0 & ~15u, whi = (total - 1) & ~15u;   // (whi = wlo or wlo + 16, < stride)
+                const uint4 a = wlo == 0 ? f : ld16(row + wlo);
+                const uint4 b = whi != wlo ? ld16(row + whi) : make_uint4(0, 0, 0, 0);
+                const uint32_t s = s0 & 15u;
+                const uint64_t d0 = pack64(a.x, a.y), d1 = pack64(a.z, a.w), d2 = pack64(b.x, b.y);
+                const uint64_t A = (s & 8u) ? d1 : d0, B = (s & 8u) ? d2 : d1;
+                const uint32_t sh = 8u * (s & 7u);
+                uint64_t v = A >> sh;
+                if (sh)
+                    v |= B << (64u - sh);
+                if (T < 8)
+                    v &= ((uint64_t)1 << (8u * T)) - 1;
+                tail = v << (8u * (8u - T));   // right-aligned
+            }
+            r0 = make_uint4(total, kRowOk | (type << 8) | ((h + inner) << 16) | (T << 24), flow, num);
+            r1 = make_uint4(D, head, (uint32_t)tail, (uint32_t)(tail >> 32));
+        }
+    }
+    st16(out + k * 32, r0);
+    st16(out + k * 32 + 16, r1);
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 
 namespace {
@@ -3987,6 +4069,9 @@ void harvest_timing(bool all)
         const EvPair& ev = g_evUsed.front();
         if (!all && hipEventQuery(ev.b) != hipSuccess)
             break;
+        // (a synchronised codec stream says nothing about the gather stream)
+        if (all && ev.kind == kBeScan)
+            (void)hipEventSynchronize(ev.b);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.a, ev.b);
         g_totalMs += ms;
@@ -4812,6 +4897,36 @@ bool be_gather(const IngestDesc* descsHost, void* descsDev, uint32_t count, cons
     return true;
 }
 
+bool be_scan_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, void* devStage,
+                  void* hostOut, void** packed, void** landed)
+{
+    bind_device();
+    *packed = *landed = nullptr;
+    hipEvent_t p = take_mark(), l = take_mark();
+    if (!p || !l) {
+        be_mark_release(p);
+        be_mark_release(l);
+        return false;
+    }
+    {
+        Timed t(kBeScan, g_gatherStream);
+        hipLaunchKernelGGL(k_scan, dim3((count + kScanThreads - 1) / kScanThreads), dim3(kScanThreads), 0,
+                           g_gatherStream, (uint64_t)(uintptr_t)rows, stride, lens, count,
+                           (uint64_t)(uintptr_t)devStage);
+    }
+    if (hipEventRecord(p, g_gatherStream) != hipSuccess)
+        return false;
+    *packed = p;
+    if (hipMemcpyAsync(hostOut, devStage, (size_t)count * sizeof(RowHead), hipMemcpyDeviceToHost,
+                       g_gatherStream) != hipSuccess ||
+        hipEventRecord(l, g_gatherStream) != hipSuccess) {
+        be_mark_release(l);
+        return false;
+    }
+    *landed = l;
+    return true;
+}
+
 bool be_mark_sync(void* mark)
 {
     bind_device();
@@ -4819,6 +4934,8 @@ bool be_mark_sync(void* mark)
         return false;
     const hipError_t e = hipEventSynchronize(static_cast<hipEvent_t>(mark));
     be_mark_release(mark);
+    if (g_timing && e == hipSuccess)   // (k_scan's bracket ends before its landed mark)
+        harvest_timing(false);
     if (e != hipSuccess) {
         check(e, "hipEventSynchronize(mark)");
         return false;

@@ -13,6 +13,7 @@
 #include "pool.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -618,6 +619,94 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv(const SgpuDecoder* decoders, unsig
     return at >= bytes && !malformed ? status : Siamese_InvalidInput;
 }
 
+namespace {
+static_assert(sizeof(SgpuRowHead) == sizeof(RowHead) && offsetof(SgpuRowHead, Status) == offsetof(RowHead, status) &&
+                  offsetof(SgpuRowHead, Flow) == offsetof(RowHead, flow) &&
+                  offsetof(SgpuRowHead, DataBytes) == offsetof(RowHead, dataBytes) &&
+                  offsetof(SgpuRowHead, Head) == offsetof(RowHead, head) &&
+                  offsetof(SgpuRowHead, Tail) == offsetof(RowHead, tail),
+              "SgpuRowHead layout");
+static_assert(SGPU_ROW_EMPTY == kRowEmpty && SGPU_ROW_OK == kRowOk && SGPU_ROW_MALFORMED == kRowMalformed,
+              "SgpuRowHead status values");
+
+// the row arguments sgpu_frames_scan_rows and sgpu_frames_recv_rows share
+inline bool rows_ok(const void* deviceRows, size_t stride, unsigned count)
+{
+    if (stride == 0 || (stride & 15) || stride > ((uint64_t)1 << 32))
+        return false;
+    if ((uintptr_t)deviceRows & 15)
+        return false;
+    return deviceRows || count == 0;
+}
+} // namespace
+
+SIAMESE_EXPORT long long sgpu_frames_scan_rows(const void* deviceRows, size_t stride, const unsigned* deviceLens,
+                                               unsigned count, SgpuRowHead* pinnedOut)
+{
+    if (!g_batchReady || !rows_ok(deviceRows, stride, count) || ((uintptr_t)deviceLens & 3) ||
+        ((uintptr_t)pinnedOut & 15) || (!pinnedOut && count > 0))
+        return -1;
+    return (long long)Engine::global()->scan_rows_async(deviceRows, stride, deviceLens, count, pinnedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_rows(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                   const SgpuRowHead* heads, const void* deviceRows, size_t stride,
+                                                   unsigned count, SiameseResult* results, unsigned* acceptedOut)
+{
+    if (!acceptedOut)
+        return Siamese_InvalidInput;
+    *acceptedOut = 0;
+    if (!rows_ok(deviceRows, stride, count) || ((!decoders || !heads) && count > 0) || ((uintptr_t)heads & 3))
+        return Siamese_InvalidInput;
+    const uint64_t dev = (uint64_t)(uintptr_t)deviceRows;
+    unsigned accepted = 0;
+    SiameseResult status = Siamese_Success;
+    for (unsigned k = 0; k < count; ++k) {
+        // (the records are the caller's memory: each is copied, checked and only then used)
+        RowHead h;
+        std::memcpy(&h, &heads[k], sizeof(h));
+        SiameseResult r = Siamese_InvalidInput;
+        if (h.status == kRowEmpty)
+            r = Siamese_NeedMoreData;
+        else if (row_head_valid(h, stride)) {
+            const uint64_t data = dev + (uint64_t)k * stride + h.headerBytes;
+            SgpuDecoder d = h.flow < decoderCount ? decoders[h.flow] : nullptr;
+            // (a decoder with a device matrix job in flight takes no packets, as in sgpu_frames_recv)
+            if (d && BD(d)->core.ge_pending())
+                d = nullptr;
+            if (d && h.type == kFrameOriginal) {
+                SiameseOriginalPacket p;
+                p.PacketNum = h.packetNum;
+                p.Data = reinterpret_cast<const unsigned char*>((uintptr_t)data);
+                p.DataBytes = h.dataBytes;
+                r = BD(d)->core.add_original(p, data);
+                ++accepted;
+            } else if (d) {
+                RowMeta m;
+                const uint8_t* tail = h.tail + 8 - h.tailBytes;
+                const int footer = read_footer(tail, h.tailBytes, &m);
+                if (footer > 0 && (unsigned)footer < h.dataBytes) {
+                    DeviceRecovery rec;
+                    rec.data = data;
+                    rec.bytes = h.dataBytes;
+                    rec.footer = h.tail + 8 - footer;
+                    rec.footerBytes = (unsigned)footer;
+                    rec.head = h.head;
+                    rec.producer = nullptr;   // ingested from the row, any alignment
+                    r = BD(d)->core.add_recovery_device(rec);
+                    ++accepted;
+                }
+            }
+        }
+        if (results)
+            results[k] = r;
+        if (r != Siamese_Success && r != Siamese_NeedMoreData && status == Siamese_Success)
+            status = r;
+    }
+    *acceptedOut = accepted;
+    return status;
+}
+
 SIAMESE_EXPORT long long sgpu_frames_send(unsigned count, const SgpuRecoveryPacket* packets, const unsigned* flows,
                                           void* pinnedOut, size_t capacity, size_t* bytesOut)
 {
@@ -666,13 +755,13 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[23] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[24] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
                             s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide,
-                            s.delivers,   s.frames};
-    for (unsigned k = 0; k < count && k < 23; ++k)
+                            s.delivers,   s.frames,      s.scans};
+    for (unsigned k = 0; k < count && k < 24; ++k)
         out[k] = v[k];
 }
 

@@ -53,6 +53,7 @@ void EngineStats::add(const EngineStats& o)
     geChainedWide += o.geChainedWide;
     delivers += o.delivers;
     frames += o.frames;
+    scans += o.scans;
 }
 
 namespace {
@@ -2926,6 +2927,47 @@ int64_t Engine::gather_async_framed(unsigned count, const void* const* srcs, con
     g.ticket = ticket;
     // later submissions may overwrite the sources (recycled buffers, the
     // next encode's packet): their device work waits for the packing
+    std::lock_guard<std::mutex> q(qMu_);
+    pendingMarks_.push_back(packed);
+    return ticket;
+}
+
+int64_t Engine::scan_rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
+                                void* pinnedOut)
+{
+    if (failed())
+        return -1;
+    std::lock_guard<std::mutex> lk(gatherMu_);
+    const int64_t ticket = ++gNext_;
+    if (count == 0)
+        return ticket;
+    GatherSlot& g = gslots_[ticket % kGatherSlots];
+    if (!gather_land(g))   // (the slot's previous gather, kGatherSlots back)
+        return -1;
+    // the records take the slot's packing area; a scan uploads no descriptors
+    const size_t total = (size_t)count * sizeof(RowHead);
+    if (total > g.stageCap) {
+        size_t c = g.stageCap ? g.stageCap : (1u << 20);
+        while (c < total)
+            c *= 2;
+        if (g.stage)
+            be_dev_free(g.stage);
+        g.stage = (uint8_t*)be_dev_alloc(c);
+        g.stageCap = g.stage ? c : 0;
+    }
+    if (!g.stage)
+        return -1;
+    void* packed = nullptr;
+    if (!be_scan_rows(rows, stride, lens, count, g.stage, pinnedOut, &packed, &g.landed)) {
+        failed_.store(true, std::memory_order_relaxed);
+        return -1;
+    }
+    g.ticket = ticket;
+    {
+        std::lock_guard<std::mutex> s(statsMu_);
+        flushStats_.scans += count;
+    }
+    // later submissions may rewrite the rows: their device work waits for the scan
     std::lock_guard<std::mutex> q(qMu_);
     pendingMarks_.push_back(packed);
     return ticket;

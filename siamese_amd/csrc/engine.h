@@ -577,6 +577,7 @@ struct EngineStats
     uint64_t geChainedWide = 0;   // chained jobs whose decode carried gated k_ldpc items (wide rows)
     uint64_t delivers = 0;        // delivery items queued (sgpu_decoder_deliver_range)
     uint64_t frames = 0;          // frame items queued (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range)
+    uint64_t scans = 0;           // rows scanned (sgpu_frames_scan_rows), counted when the scan is queued
 
     void add(const EngineStats& o);
 };
@@ -673,6 +674,13 @@ public:
     /// align16(hdrLens[k] + bytes[k]) over k < i, zero-padded (framed egress).
     int64_t gather_async_framed(unsigned count, const void* const* srcs, const unsigned* bytes,
                                 const uint8_t* hdrs, const unsigned* hdrLens, void* pinnedOut);
+    /// A gather of another kind on the same slots and tickets: one RowHead
+    /// (ops.h) per frame row of rows + k * stride, k < count, into pinnedOut
+    /// (k_scan, sgpu_frames_scan_rows).  lens: the rows' length words in
+    /// device memory, or null.  The rows are read before any later
+    /// submission's device work, as a gather's sources are.
+    int64_t scan_rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
+                            void* pinnedOut);
     /// Wait until gather `ticket` and every earlier one have landed.
     bool gather_wait(int64_t ticket);
     /// Host -> device copy on the staging stream, issued now; every later

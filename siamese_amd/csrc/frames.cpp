@@ -5,8 +5,8 @@
 namespace sgpu {
 
 namespace {
-constexpr unsigned kOriginalHeader = 1 + kFrameFlowBytes + 3;   // type, flow, PacketNum
-constexpr unsigned kRecoveryHeader = 1 + kFrameFlowBytes;       // type, flow
+constexpr unsigned kOriginalHeader = kFrameOriginalInner;
+constexpr unsigned kRecoveryHeader = kFrameRecoveryInner;
 
 inline unsigned prefix_bytes(unsigned length)
 {

@@ -15,8 +15,13 @@
 // boundary).
 #pragma once
 
+#include "codedef.h"
+#include "ops.h"
+#include "../../include/siamese.h"
+
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 namespace sgpu {
 
@@ -24,6 +29,9 @@ constexpr uint8_t kFrameOriginal = 0;
 constexpr uint8_t kFrameRecovery = 1;
 constexpr unsigned kFrameFlowBytes = 3;
 constexpr unsigned kFrameMaxFlow = (1u << 24) - 1;
+/// Bytes between a frame's length prefix and its data.
+constexpr unsigned kFrameOriginalInner = 1 + kFrameFlowBytes + 3;   // type, flow, PacketNum
+constexpr unsigned kFrameRecoveryInner = 1 + kFrameFlowBytes;       // type, flow
 
 /// One parsed frame: byte offsets into the buffer it was parsed from.
 struct FrameInfo
@@ -48,5 +56,73 @@ constexpr size_t kNoBadFrame = ~(size_t)0;
 /// Stops early (returning maxFrames) when out is full: *consumed says how far.
 long frames_parse(const uint8_t* buf, size_t bytes, FrameInfo* out, size_t maxFrames, size_t* consumed,
                   size_t* badOffset);
+
+/// Frame rows in device memory (ops.h RowHead, sgpu_frames_scan_rows /
+/// sgpu_frames_recv_rows).  The one definition of a record that may be acted
+/// on, for a row of `stride` bytes: status kRowOk; a type the format has; at
+/// least one data byte (L > the type's inner header) and at most
+/// SIAMESE_MAX_PACKET_BYTES; a header of the type's inner bytes plus a 1-4
+/// byte prefix; header + data within the stride and within frameBytes; a flow
+/// of three bytes; an original's PacketNum <= SIAMESE_PACKET_NUM_MAX;
+/// tailBytes = min(8, dataBytes) for a recovery packet, 0 for an original.
+/// sgpu_frames_recv_rows trusts no record that fails it, and row_head_scan
+/// (so the test double of k_scan) reports such a row malformed.  (Defined
+/// here: the test double is also built without frames.cpp.)
+inline bool row_head_valid(const RowHead& r, uint64_t stride)
+{
+    if (r.status != kRowOk || r.type > kFrameRecovery)
+        return false;
+    const unsigned inner = r.type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+    if (r.dataBytes < 1 || r.dataBytes > SIAMESE_MAX_PACKET_BYTES)
+        return false;
+    if (r.headerBytes < inner + 1 || r.headerBytes > inner + 4)
+        return false;
+    const uint64_t end = (uint64_t)r.headerBytes + r.dataBytes;
+    if (end > stride || end > r.frameBytes)
+        return false;
+    if (r.flow > kFrameMaxFlow)
+        return false;
+    if (r.type == kFrameOriginal)
+        return r.packetNum <= SIAMESE_PACKET_NUM_MAX && r.tailBytes == 0;
+    return r.tailBytes == (r.dataBytes < 8 ? r.dataBytes : 8u);
+}
+
+/// What k_scan computes for one row: row[0, stride) in host memory, len = the
+/// row's length word or null.  The prefix is judged as frames_parse judges it
+/// (a zero L is malformed, a prefix wider than its L needs is not).
+inline void row_head_scan(const uint8_t* row, uint64_t stride, const uint32_t* len, RowHead* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    if (len ? *len == 0 : row[0] == 0)
+        return;   // kRowEmpty
+    RowHead r;
+    std::memset(&r, 0, sizeof(r));
+    unsigned length = 0;
+    const int h = read_length_prefix(row, 4, &length);   // (a row has 16 bytes at least)
+    bool ok = h >= 1 && length >= 1 && (!len || *len == (uint64_t)h + length);
+    if (ok) {
+        const uint8_t* f = row + h;   // type, flow, PacketNum: within the row's first 11 bytes
+        r.status = kRowOk;
+        r.type = f[0];
+        const unsigned inner = r.type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+        r.frameBytes = (uint32_t)h + length;
+        r.headerBytes = (uint8_t)(h + inner);
+        r.flow = f[1] | ((uint32_t)f[2] << 8) | ((uint32_t)f[3] << 16);
+        r.packetNum = r.type == kFrameOriginal ? f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) : 0;
+        r.dataBytes = length > inner ? length - inner : 0;
+        r.tailBytes = r.type == kFrameRecovery ? (uint8_t)(r.dataBytes < 8 ? r.dataBytes : 8) : 0;
+        ok = row_head_valid(r, stride);
+    }
+    if (!ok) {
+        out->status = kRowMalformed;
+        return;
+    }
+    if (r.type == kFrameRecovery) {
+        const uint8_t* data = row + r.headerBytes;
+        std::memcpy(r.head, data, r.dataBytes < 4 ? r.dataBytes : 4);
+        std::memcpy(r.tail + 8 - r.tailBytes, data + r.dataBytes - r.tailBytes, r.tailBytes);
+    }
+    *out = r;
+}
 
 } // namespace sgpu

@@ -442,6 +442,38 @@ static_assert(sizeof(FrameItem) == 48, "FrameItem layout");
 /// k_frame's grid is k_deliver's: kDeliverWaves items per workgroup, at most
 /// kDeliverMaxChunks chunk rows.
 
+/// What the host needs of one frame row that lives in device memory (k_scan,
+/// sgpu_frames_scan_rows): the layout of SgpuRowHead (include/siamese_gpu.h),
+/// written as eight dwords
+///   [0] frameBytes  [1] status | type << 8 | headerBytes << 16 | tailBytes << 24
+///   [2] flow  [3] packetNum  [4] dataBytes  [5] head  [6..7] tail.
+/// Row k starts at rows + k * stride (16-byte aligned, stride a multiple of
+/// 16).  With a length array, lens[k] == 0 makes the row empty and a non-zero
+/// word must equal the frame's prefix + L; without one a zero first byte does.
+/// Otherwise the row's first 16 bytes are parsed as a frame header (frames.h)
+/// and checked (frames.h row_head_valid states the checks); a recovery row
+/// also gives its first min(4, dataBytes) bytes (head) and its last
+/// tailBytes = min(8, dataBytes) bytes, right-aligned in tail.  An empty or
+/// malformed record is zero but for its status.  Nothing outside
+/// [row, row + stride) and the row's length word is read.
+constexpr uint8_t kRowEmpty = 0, kRowOk = 1, kRowMalformed = 2;
+struct RowHead
+{
+    uint32_t frameBytes;   // prefix + L (0: empty or malformed)
+    uint8_t status;        // kRowEmpty / kRowOk / kRowMalformed
+    uint8_t type;          // kFrameOriginal / kFrameRecovery
+    uint8_t headerBytes;   // offset of the data in the row (<= kFrameMaxHeader)
+    uint8_t tailBytes;
+    uint32_t flow;
+    uint32_t packetNum;    // originals
+    uint32_t dataBytes;
+    uint8_t head[4];
+    uint8_t tail[8];
+};
+static_assert(sizeof(RowHead) == 32, "RowHead layout");
+/// k_scan: one lane per row, kScanThreads rows per workgroup.
+constexpr uint32_t kScanThreads = 256;
+
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)
 /// Solves with more rows than this stage 256-byte tiles (16 lanes x 16 bytes

@@ -10,6 +10,7 @@
 #include "../siamese_amd/csrc/backend.h"
 #include "../siamese_amd/csrc/gf.h"
 #include "../siamese_amd/csrc/codedef.h"
+#include "../siamese_amd/csrc/frames.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -631,6 +632,20 @@ bool be_gather(const IngestDesc* descsHost, void* descsDev, uint32_t count, cons
     std::memcpy(descsDev, descsHost, (size_t)count * sizeof(IngestDesc));
     be_launch_ingest(BeIngest{static_cast<const IngestDesc*>(descsDev), count, 0});
     std::memcpy(hostOut, devStage, bytes);
+    return true;
+}
+
+// k_scan (ops.h RowHead): one record per row, computed by the host statement
+// of the same rules (frames.h row_head_scan); synchronous like be_gather.
+bool be_scan_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, void* devStage,
+                  void* hostOut, void** packed, void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    RowHead* out = static_cast<RowHead*>(devStage);
+    for (uint32_t k = 0; k < count; ++k)
+        row_head_scan(static_cast<const uint8_t*>(rows) + (uint64_t)k * stride, stride, lens ? lens + k : nullptr,
+                      out + k);
+    std::memcpy(hostOut, devStage, (size_t)count * sizeof(RowHead));
     return true;
 }
 
