@@ -508,6 +508,128 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_rows(const SgpuDecoder* decoders, 
                                                    unsigned count, SiameseResult* results /* optional */,
                                                    unsigned* acceptedOut);
 
+/*
+    Rows that hold several frames: an MTU-sized datagram that carries a few
+    small originals and the recovery packet that protects them, frames
+    following each other as "Framed datagrams" allows (zero bytes between
+    them are skipped).  The two calls above take one frame per row from the
+    row's first byte; these take every frame of a row, at any byte offset:
+
+        bytes  = sgpu_frames_packed_bytes(count, maxFrames);      // pinned, sgpu_host_alloc
+        ticket = sgpu_frames_scan_packed(rows, stride, lens, count, maxFrames, out);
+        sgpu_gather_wait(ticket);
+        sgpu_frames_recv_packed(decoders, n, out, maxFrames, rows, stride, count, results, &accepted);
+
+    out holds count * maxFrames SgpuPackedHead records, row k's at index
+    k * maxFrames, and after them count uint32 row words: SGPU_PACKED_COUNT
+    records of the row are SGPU_ROW_OK (its first ones, in the order of the
+    frames), every other record is zero.  sgpu_encoder_pack_frames (below)
+    builds such rows on the device.
+*/
+#define SGPU_PACKED_MORE      0x80000000u  /* frames (non-zero bytes) remain after maxFrames records */
+#define SGPU_PACKED_MALFORMED 0x40000000u  /* the walk stopped at a frame it could not accept */
+#define SGPU_PACKED_COUNT(w)  ((w) & 0xffffu)
+
+/// One frame's record: 32 bytes, SgpuRowHead with Offset in place of FrameBytes.
+typedef struct SgpuPackedHead
+{
+    unsigned      Offset;      ///< byte offset of the frame's first byte (its length prefix) in the row
+    unsigned char Status;      ///< SGPU_ROW_OK; SGPU_ROW_EMPTY (a zero record) past the row's last frame
+    unsigned char Type;        ///< as SgpuRowHead
+    unsigned char HeaderBytes; ///< the data is at Offset + HeaderBytes (HeaderBytes <= 11)
+    unsigned char TailBytes;
+    unsigned      Flow;
+    unsigned      PacketNum;
+    unsigned      DataBytes;
+    unsigned char Head[4];
+    unsigned char Tail[8];
+} SgpuPackedHead;
+#if defined(__cplusplus)
+static_assert(sizeof(SgpuPackedHead) == 32, "SgpuPackedHead is 32 bytes");
+#else
+_Static_assert(sizeof(SgpuPackedHead) == 32, "SgpuPackedHead is 32 bytes");
+#endif
+
+/// Bytes of a packed scan's output: count * maxFrames records, then count row
+/// words (0 for maxFrames outside 1..256).
+SIAMESE_EXPORT size_t sgpu_frames_packed_bytes(unsigned count, unsigned maxFrames);
+/// Scan `count` rows of up to maxFrames (1..256) frames each into pinnedOut
+/// (pinned, 16-byte aligned, sgpu_frames_packed_bytes) with one kernel launch:
+/// a gather with sgpu_frames_scan_rows' contract, tickets and arguments.  Every
+/// record and every row word is written by every scan.
+///
+/// Row k, with end = deviceLens ? deviceLens[k] : stride:
+///   - deviceLens[k] == 0: an empty row whatever bytes it holds, row word 0;
+///   - deviceLens[k] > stride: row word SGPU_PACKED_MALFORMED, no records;
+///   - otherwise the records are the frames sgpu_frames_parse finds in
+///     row[0, end), in order: zero bytes where a frame would start are skipped,
+///     the prefix is judged with the bytes that remain before end, and a frame
+///     is accepted under sgpu_frames_scan_rows' per-frame rules with
+///     Offset + HeaderBytes + DataBytes <= end.  The first frame that is not
+///     accepted ends the row's walk: the frames before it are reported and
+///     SGPU_PACKED_MALFORMED is set.  It never affects another row.
+///   - after maxFrames records the walk stops, and SGPU_PACKED_MORE is set if a
+///     non-zero byte remains before end (scan again with a larger maxFrames).
+/// Bytes in [end, stride) are ignored (they may be read); nothing outside
+/// [row, row + stride) and the row's length word is read.
+///
+/// Returns -1, with nothing queued, as sgpu_frames_scan_rows does, and for
+/// maxFrames outside 1..256 or an output above 4 GiB.  count == 0 returns a
+/// valid ticket that is already complete.
+SIAMESE_EXPORT long long sgpu_frames_scan_packed(const void* deviceRows, size_t stride, const unsigned* deviceLens,
+                                                 unsigned count, unsigned maxFrames, void* pinnedOut);
+/// Host only: sgpu_frames_recv_rows for a packed scan's output (`heads`, 4-byte
+/// aligned): for row k the first min(SGPU_PACKED_COUNT(word k), maxFrames)
+/// records are routed in order, record j's data being at deviceRows + k*stride
+/// + Offset + HeaderBytes.  results[k*maxFrames + j] (optional, count *
+/// maxFrames entries) = the result for record j of row k, as
+/// sgpu_frames_recv_rows gives it; unused slots get Siamese_NeedMoreData.  A row
+/// whose word has SGPU_PACKED_MALFORMED contributes Siamese_InvalidInput to the
+/// return value after its good frames have been delivered.  The records and
+/// words are caller data and never trusted: each is copied and checked against
+/// stride before use; a record that fails, or a word whose count exceeds
+/// maxFrames, counts as malformed.  *acceptedOut = the frames handed to a
+/// decoder.  Arguments are refused as in sgpu_frames_recv_rows, and for
+/// maxFrames outside 1..256.  For well-formed rows the decoders end in the
+/// state sgpu_frames_recv leaves them in, given a host copy of the same bytes.
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_packed(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                     const void* heads, unsigned maxFrames, const void* deviceRows,
+                                                     size_t stride, unsigned count,
+                                                     SiameseResult* results /* count*maxFrames, optional */,
+                                                     unsigned* acceptedOut);
+/// Queue a stream's frames packed into MTU-sized rows: the present originals
+/// firstPacketNum .. firstPacketNum+originalCount-1 of `encoder`, ascending, as
+/// SGPU_FRAME_ORIGINAL, then `recovery` (this encoder's current output) as
+/// SGPU_FRAME_RECOVERY, all for `flow`.  Absent originals get results[k] =
+/// Siamese_NeedMoreData and take no space.
+///
+/// The layout is decided here, by one rule: a cursor (row, off) starts at
+/// (0, 0); a frame of T = header + data bytes that does not fit (off + T >
+/// stride) moves to (row + 1, 0); the frame is placed at off and off becomes
+/// align16(off + T).  So frames start on 16-byte boundaries with zeros between
+/// them.  Rows [0, *rowsOut) are written whole (zero between the frames and to
+/// the row's end), deviceLens[row] = the end of the row's last frame;
+/// deviceLens[r] = 0 for r in [*rowsOut, maxRows) and those rows are left
+/// untouched.  The buffer is a valid frame stream for sgpu_frames_parse /
+/// sgpu_frames_recv and valid input for sgpu_frames_scan_packed.  *framesOut =
+/// the frames queued.  Never waits; the rows and lengths are in place when the
+/// call's submission has completed (the lifetime rule of the deliver calls).
+///
+/// Siamese_InvalidInput, with nothing queued: the deliver calls' pointer,
+/// alignment and stride rules (deviceDst and deviceLens may be null only when
+/// maxRows is 0); a null encoder, rowsOut or framesOut; null recovery with
+/// recoveryCount > 0; flow > 2^24-1 (SGPU_FRAME_NONE included: bare packets
+/// cannot be delimited); firstPacketNum > SIAMESE_PACKET_NUM_MAX; a frame with
+/// T > stride; a recovery packet that is not this encoder's (or is empty);
+/// more rows needed than maxRows, *rowsOut then saying how many were needed.
+/// A disabled encoder returns Siamese_Disabled.
+SIAMESE_EXPORT SiameseResult sgpu_encoder_pack_frames(SgpuEncoder encoder, unsigned flow, unsigned firstPacketNum,
+                                                      unsigned originalCount, const SgpuRecoveryPacket* recovery,
+                                                      unsigned recoveryCount, void* deviceDst, size_t stride,
+                                                      unsigned maxRows, unsigned* deviceLens,
+                                                      SiameseResult* results /* host, originalCount, optional */,
+                                                      unsigned* rowsOut, unsigned* framesOut);
+
 /// Device timing of flushed work since the last reset (milliseconds).
 SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* totalMs);
 /// Device milliseconds per kernel class since the last sgpu_timing reset,
@@ -517,7 +639,8 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// [5] k_deliver (sgpu_decoder_deliver_range), [6] k_frame
 /// (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range), [7] k_scan
 /// (sgpu_frames_scan_rows: launched on the gather stream, counted once its
-/// gather has been waited for); count entries at most.
+/// gather has been waited for), [8] k_walk (sgpu_frames_scan_packed,
+/// likewise); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -537,7 +660,8 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// ones included, counted when their submission is laid out), then [22] the
 /// frame items queued likewise (sgpu_frames_deliver_recovery,
 /// sgpu_encoder_deliver_range), then [23] the rows scanned
-/// (sgpu_frames_scan_rows, counted when the scan is queued); count entries at
+/// (sgpu_frames_scan_rows, counted when the scan is queued), then [24] the
+/// rows scanned by sgpu_frames_scan_packed, counted likewise; count entries at
 /// most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'

@@ -46,6 +46,31 @@ def bind_rows_abi(L):
     return L
 
 
+class PackedHead(ctypes.Structure):
+    """SgpuPackedHead (siamese_gpu.h): one frame of a row that holds several,
+    32 bytes; RowHead with the frame's offset in the row for FrameBytes."""
+    _fields_ = [("Offset", ctypes.c_uint)] + RowHead._fields_[1:]
+
+
+PACKED_MORE, PACKED_MALFORMED, PACKED_COUNT_MASK = 0x80000000, 0x40000000, 0xffff
+
+
+def bind_packed_abi(L):
+    """Prototypes of the siamese_gpu.h calls for rows that hold several frames
+    (and of bind_rows_abi's calls, which they share tickets with)."""
+    vp, u, sz = ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t
+    bind_rows_abi(L)
+    L.sgpu_frames_packed_bytes.restype = sz
+    L.sgpu_frames_packed_bytes.argtypes = [u, u]
+    L.sgpu_frames_scan_packed.restype = ctypes.c_longlong
+    L.sgpu_frames_scan_packed.argtypes = [vp, sz, vp, u, u, vp]
+    L.sgpu_frames_recv_packed.restype = ctypes.c_int
+    L.sgpu_frames_recv_packed.argtypes = [vp, u, vp, u, vp, sz, u, vp, vp]
+    L.sgpu_encoder_pack_frames.restype = ctypes.c_int
+    L.sgpu_encoder_pack_frames.argtypes = [vp, u, u, u, vp, u, vp, sz, u, vp, vp, vp, vp]
+    return L
+
+
 class SiameseError(RuntimeError):
     def __init__(self, what, code):
         name = RESULT_NAMES[code] if 0 <= code < 6 else str(code)

@@ -142,8 +142,9 @@ void be_join_ge();
 void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStride);
 /// A sender's packets framed into caller-owned rows (ops.h FrameItem), the
 /// grid and maxStride as be_launch_deliver's: each row gets its literal
-/// header, the packet and a zero tail, and its length word (zero, and an
-/// untouched row, for an absent packet).  Queued beside be_launch_deliver.
+/// header, the packet and a zero tail, and its length word when the item has
+/// one (lenBase, and an untouched row, for an absent packet).  Queued beside
+/// be_launch_deliver.
 void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t maxStride);
 
 /// Block until all queued work has finished.  Returns false on a device fault.
@@ -184,6 +185,12 @@ bool be_gather(const IngestDesc* descsHost, void* descsDev, uint32_t count, cons
 /// hostOut holds the records.  False if it could not be queued.
 bool be_scan_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, void* devStage,
                   void* hostOut, void** packed, void** landed);
+/// One k_walk launch on the gather stream (ops.h PackedHead): maxFrames
+/// records per row and then one word per row into devStage (packed_bytes(count,
+/// maxFrames), device memory), then one copy of all of it to hostOut (pinned),
+/// without waiting.  rows, stride, lens and the marks are be_scan_rows'.
+bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                  void* devStage, void* hostOut, void** packed, void** landed);
 /// Block until the device has passed `mark`, then recycle it; false on a
 /// device fault.
 bool be_mark_sync(void* mark);
@@ -191,9 +198,21 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-/// (kBeScan is bracketed on the gather stream: be_sync waits for a bracket of
-/// that class still in flight before it folds it in)
-enum BeKernel { kBeIngest, kBeExec, kBeLdpc, kBeSolve, kBeGe, kBeDeliver, kBeFrame, kBeScan, kBeKernelKinds };
+/// (kBeScan and kBeWalk are bracketed on the gather stream: be_sync waits for a
+/// bracket of those classes still in flight before it folds it in)
+enum BeKernel
+{
+    kBeIngest,
+    kBeExec,
+    kBeLdpc,
+    kBeSolve,
+    kBeGe,
+    kBeDeliver,
+    kBeFrame,
+    kBeScan,
+    kBeWalk,
+    kBeKernelKinds
+};
 void be_timing_enable(bool on);
 /// Device milliseconds of one kernel class since the last reset.
 double be_timing_kernel_ms(BeKernel kind);

@@ -22,6 +22,7 @@
 //   k_frame        a sender's originals and recovery packets as wire frames
 //                  into caller-owned rows (header, packet, zero tail; opt-in)
 //   k_scan         frame rows in device memory into 32-byte host records
+//   k_walk         rows that hold several frames into one record per frame
 //                  (header fields, a recovery packet's head and tail; opt-in)
 //
 // GF(256) multiply by a wave-uniform constant uses three v_perm_b32 byte
@@ -3827,8 +3828,8 @@ __global__ __launch_bounds__(64 * kDeliverWaves) void k_frame(const FrameItem* _
     const uint64_t stride = (uint64_t)it.stride16 << 4;
     const uint32_t hl = it.hdrLen;
     const uint64_t total = it.src != 0 ? (uint64_t)hl + it.bytes : 0;   // (<= stride: the host checked)
-    if (blockIdx.y == 0 && lane == 0)
-        *reinterpret_cast<GMEM uint32_t*>(it.lenOut) = (uint32_t)total;
+    if (blockIdx.y == 0 && lane == 0 && it.lenOut != 0)   // (none: not the last frame of a packed row)
+        *reinterpret_cast<GMEM uint32_t*>(it.lenOut) = it.lenBase + (uint32_t)total;
     if (it.src == 0)   // an absent packet: its row stays as it is
         return;
     // source address that lines up with row byte 0
@@ -3971,6 +3972,138 @@ __global__ __launch_bounds__(kScanThreads) void k_scan(uint64_t rows, uint64_t s
 }
 
 // ---------------------------------------------------------------------------
+// Packed row walk (k_walk, ops.h PackedHead)
+//
+// k_scan for rows that hold several frames: still one lane per row, but the
+// lane walks its row as frames_parse does (frames.h row_walk is the
+// statement) and writes one 32-byte record per frame, then zero records up to
+// maxFrames and the row word.  The cursor moves through aligned 16-byte
+// words: the word that holds it is loaded, the bytes before the cursor and
+// at or past the row's end are masked off, and the first non-zero byte that
+// is left starts a frame (none: the whole word is skipped, so a zero run costs
+// one load per 16 bytes).  A header of up to 11 bytes at byte s of its word
+// needs the next word when s > 4; that word is loaded only if it lies inside
+// the row, and the 16 bytes from the cursor are the three or four 64-bit
+// halves recombined by shifts, after which the fields are k_scan's.  Every
+// header byte that is used lies before the row's end, because the prefix is
+// judged with the bytes left and the frame must fit; so does the tail, taken
+// as in k_scan from the one or two words that hold it.  A frame's walk is a
+// chain of dependent loads (the next header's place is known only from this
+// one's length), so a lane has one request in flight, and the lanes of a wave
+// stay 64 rows apart: the kernel is bound by request latency times frames
+// per row, not by bytes.  No LDS, no atomics.
+
+// mask of the low n bytes of a qword, n clamped to [0, 8]
+__device__ __forceinline__ uint64_t low_bytes64(int64_t n)
+{
+    return n <= 0 ? 0ull : (n >= 8 ? ~0ull : (((uint64_t)1 << (8 * n)) - 1));
+}
+
+__global__ __launch_bounds__(kWalkThreads) void k_walk(uint64_t rows, uint64_t stride,
+                                                       const uint32_t* __restrict__ lens, uint32_t count,
+                                                       uint32_t maxFrames, uint64_t out)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kWalkThreads + threadIdx.x;
+    if (k >= count)
+        return;
+    const uint64_t row = rows + k * stride;
+    const uint64_t rec = out + k * maxFrames * 32;
+    uint64_t end = lens ? lens[k] : stride;
+    uint32_t n = 0, flags = 0;
+    if (end > stride) {
+        flags = kPackedMalformed;
+        end = 0;
+    }
+    uint64_t at = 0;
+    while (at < end) {
+        const uint64_t wa = at & ~(uint64_t)15;
+        const uint4 A = ld16(row + wa);
+        const uint64_t d0 = pack64(A.x, A.y), d1 = pack64(A.z, A.w);
+        // the word's bytes in [at, end)
+        const int64_t lo = (int64_t)(at - wa), hi = (int64_t)(end - wa);
+        const uint64_t m0 = d0 & low_bytes64(hi) & ~low_bytes64(lo);
+        const uint64_t m1 = d1 & low_bytes64(hi - 8) & ~low_bytes64(lo - 8);
+        if ((m0 | m1) == 0) {
+            at = wa + 16;
+            continue;
+        }
+        const uint32_t s = m0 ? (uint32_t)(__ffsll((long long)m0) - 1) >> 3
+                              : 8u + ((uint32_t)(__ffsll((long long)m1) - 1) >> 3);
+        at = wa + s;
+        if (n == maxFrames) {
+            flags |= kPackedMore;
+            break;
+        }
+        // row bytes [at, at + 16), zero where the next word is not loaded
+        const uint4 B = (s > 4 && wa + 16 < stride) ? ld16(row + wa + 16) : make_uint4(0, 0, 0, 0);
+        const uint64_t d2 = pack64(B.x, B.y), d3 = pack64(B.z, B.w);
+        const uint64_t P = (s & 8u) ? d1 : d0, Q = (s & 8u) ? d2 : d1, R = (s & 8u) ? d3 : d2;
+        const uint32_t sh = 8u * (s & 7u);
+        uint64_t w0 = P >> sh, w1 = Q >> sh;
+        if (sh) {
+            w0 |= Q << (64u - sh);
+            w1 |= R << (64u - sh);
+        }
+        const uint64_t left = end - at;
+        uint32_t L = 0;
+        const int hp = parse_prefix((uint32_t)w0, left < 4 ? (uint32_t)left : 4u, &L);
+        bool ok = hp >= 1 && L >= 1 && (uint64_t)hp + L <= left;
+        uint4 r0 = make_uint4(0, 0, 0, 0), r1 = make_uint4(0, 0, 0, 0);
+        uint32_t total = 0;
+        if (ok) {
+            const uint32_t h = (uint32_t)hp;
+            // row bytes [at + h, at + h + 8): type, flow, then PacketNum or the packet's first bytes
+            const uint64_t x = (w0 >> (8u * h)) | (w1 << (64u - 8u * h));
+            const uint32_t type = (uint32_t)x & 0xffu;
+            const uint32_t inner = type == 0 ? 7u : 4u;
+            const uint32_t flow = (uint32_t)(x >> 8) & 0xffffffu;
+            const uint32_t num = type == 0 ? (uint32_t)(x >> 32) & 0xffffffu : 0u;
+            total = h + L;   // (L < 2^29)
+            ok = type <= 1 && L > inner && num <= 0x3fffffu;
+            if (ok) {
+                const uint32_t D = L - inner;
+                uint32_t head = 0, T = 0;
+                uint64_t tail = 0;
+                if (type == 1) {
+                    head = (uint32_t)(x >> 32) & byte_mask((int)D);
+                    T = D < 8 ? D : 8;
+                    const uint64_t fe = at + total;   // the tail is row bytes [fe - T, fe), fe <= end
+                    const uint64_t s0 = fe - T;
+                    const uint64_t wlo = s0 & ~(uint64_t)15, whi = (fe - 1) & ~(uint64_t)15;   // (whi < stride)
+                    const uint4 a = wlo == wa ? A : ld16(row + wlo);
+                    const uint4 b = whi != wlo ? ld16(row + whi) : make_uint4(0, 0, 0, 0);
+                    const uint32_t ts = (uint32_t)s0 & 15u;
+                    const uint64_t e0 = pack64(a.x, a.y), e1 = pack64(a.z, a.w), e2 = pack64(b.x, b.y);
+                    const uint64_t TA = (ts & 8u) ? e1 : e0, TB = (ts & 8u) ? e2 : e1;
+                    const uint32_t tsh = 8u * (ts & 7u);
+                    uint64_t v = TA >> tsh;
+                    if (tsh)
+                        v |= TB << (64u - tsh);
+                    if (T < 8)
+                        v &= ((uint64_t)1 << (8u * T)) - 1;
+                    tail = v << (8u * (8u - T));   // right-aligned
+                }
+                r0 = make_uint4((uint32_t)at, kRowOk | (type << 8) | ((h + inner) << 16) | (T << 24), flow, num);
+                r1 = make_uint4(D, head, (uint32_t)tail, (uint32_t)(tail >> 32));
+            }
+        }
+        if (!ok) {
+            flags |= kPackedMalformed;
+            break;
+        }
+        st16(rec + (uint64_t)n * 32, r0);
+        st16(rec + (uint64_t)n * 32 + 16, r1);
+        ++n;
+        at += total;
+    }
+    for (uint32_t j = n; j < maxFrames; ++j) {   // every record is written by every scan
+        st16(rec + (uint64_t)j * 32, make_uint4(0, 0, 0, 0));
+        st16(rec + (uint64_t)j * 32 + 16, make_uint4(0, 0, 0, 0));
+    }
+    *reinterpret_cast<GMEM uint32_t*>(out + (uint64_t)count * maxFrames * 32 + k * 4) = n | flags;
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 
 namespace {
@@ -4070,7 +4203,7 @@ void harvest_timing(bool all)
         if (!all && hipEventQuery(ev.b) != hipSuccess)
             break;
         // (a synchronised codec stream says nothing about the gather stream)
-        if (all && ev.kind == kBeScan)
+        if (all && (ev.kind == kBeScan || ev.kind == kBeWalk))
             (void)hipEventSynchronize(ev.b);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.a, ev.b);
@@ -4927,6 +5060,36 @@ bool be_scan_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint3
     return true;
 }
 
+bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                  void* devStage, void* hostOut, void** packed, void** landed)
+{
+    bind_device();
+    *packed = *landed = nullptr;
+    hipEvent_t p = take_mark(), l = take_mark();
+    if (!p || !l) {
+        be_mark_release(p);
+        be_mark_release(l);
+        return false;
+    }
+    {
+        Timed t(kBeWalk, g_gatherStream);
+        hipLaunchKernelGGL(k_walk, dim3((count + kWalkThreads - 1) / kWalkThreads), dim3(kWalkThreads), 0,
+                           g_gatherStream, (uint64_t)(uintptr_t)rows, stride, lens, count, maxFrames,
+                           (uint64_t)(uintptr_t)devStage);
+    }
+    if (hipEventRecord(p, g_gatherStream) != hipSuccess)
+        return false;
+    *packed = p;
+    if (hipMemcpyAsync(hostOut, devStage, (size_t)packed_bytes(count, maxFrames), hipMemcpyDeviceToHost,
+                       g_gatherStream) != hipSuccess ||
+        hipEventRecord(l, g_gatherStream) != hipSuccess) {
+        be_mark_release(l);
+        return false;
+    }
+    *landed = l;
+    return true;
+}
+
 bool be_mark_sync(void* mark)
 {
     bind_device();
@@ -4934,7 +5097,7 @@ bool be_mark_sync(void* mark)
         return false;
     const hipError_t e = hipEventSynchronize(static_cast<hipEvent_t>(mark));
     be_mark_release(mark);
-    if (g_timing && e == hipSuccess)   // (k_scan's bracket ends before its landed mark)
+    if (g_timing && e == hipSuccess)   // (k_scan's and k_walk's bracket ends before its landed mark)
         harvest_timing(false);
     if (e != hipSuccess) {
         check(e, "hipEventSynchronize(mark)");

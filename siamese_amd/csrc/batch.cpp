@@ -40,6 +40,44 @@ inline BatchEncoder* BE(SgpuEncoder e) { return reinterpret_cast<BatchEncoder*>(
 inline BatchDecoder* BD(SgpuDecoder d) { return reinterpret_cast<BatchDecoder*>(d); }
 using Lock = std::lock_guard<std::mutex>;
 
+// The routing sgpu_frames_recv_rows and sgpu_frames_recv_packed share: a
+// record that passed its check (RowHead / PackedHead: the same fields), with
+// its data at `data`, goes to its flow's decoder.
+template <class Head>
+SiameseResult route_head(const SgpuDecoder* decoders, unsigned decoderCount, const Head& h, uint64_t data,
+                         unsigned* accepted)
+{
+    SiameseResult r = Siamese_InvalidInput;
+    SgpuDecoder d = h.flow < decoderCount ? decoders[h.flow] : nullptr;
+    // (a decoder with a device matrix job in flight takes no packets, as in sgpu_frames_recv)
+    if (d && BD(d)->core.ge_pending())
+        d = nullptr;
+    if (d && h.type == kFrameOriginal) {
+        SiameseOriginalPacket p;
+        p.PacketNum = h.packetNum;
+        p.Data = reinterpret_cast<const unsigned char*>((uintptr_t)data);
+        p.DataBytes = h.dataBytes;
+        r = BD(d)->core.add_original(p, data);
+        ++*accepted;
+    } else if (d) {
+        RowMeta m;
+        const uint8_t* tail = h.tail + 8 - h.tailBytes;
+        const int footer = read_footer(tail, h.tailBytes, &m);
+        if (footer > 0 && (unsigned)footer < h.dataBytes) {
+            DeviceRecovery rec;
+            rec.data = data;
+            rec.bytes = h.dataBytes;
+            rec.footer = h.tail + 8 - footer;
+            rec.footerBytes = (unsigned)footer;
+            rec.head = h.head;
+            rec.producer = nullptr;   // ingested from the row, any alignment
+            r = BD(d)->core.add_recovery_device(rec);
+            ++*accepted;
+        }
+    }
+    return r;
+}
+
 } // namespace
 
 extern "C" {
@@ -638,6 +676,17 @@ inline bool rows_ok(const void* deviceRows, size_t stride, unsigned count)
         return false;
     return deviceRows || count == 0;
 }
+
+static_assert(sizeof(SgpuPackedHead) == sizeof(PackedHead) && offsetof(SgpuPackedHead, Offset) == offsetof(PackedHead, offset) &&
+                  offsetof(SgpuPackedHead, Status) == offsetof(PackedHead, status) &&
+                  offsetof(SgpuPackedHead, Flow) == offsetof(PackedHead, flow) &&
+                  offsetof(SgpuPackedHead, DataBytes) == offsetof(PackedHead, dataBytes) &&
+                  offsetof(SgpuPackedHead, Head) == offsetof(PackedHead, head) &&
+                  offsetof(SgpuPackedHead, Tail) == offsetof(PackedHead, tail),
+              "SgpuPackedHead layout");
+static_assert(SGPU_PACKED_MORE == kPackedMore && SGPU_PACKED_MALFORMED == kPackedMalformed &&
+                  SGPU_PACKED_COUNT(0xffffffffu) == kPackedCountMask,
+              "SgpuPackedHead row word");
 } // namespace
 
 SIAMESE_EXPORT long long sgpu_frames_scan_rows(const void* deviceRows, size_t stride, const unsigned* deviceLens,
@@ -668,36 +717,8 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_rows(const SgpuDecoder* decoders, 
         SiameseResult r = Siamese_InvalidInput;
         if (h.status == kRowEmpty)
             r = Siamese_NeedMoreData;
-        else if (row_head_valid(h, stride)) {
-            const uint64_t data = dev + (uint64_t)k * stride + h.headerBytes;
-            SgpuDecoder d = h.flow < decoderCount ? decoders[h.flow] : nullptr;
-            // (a decoder with a device matrix job in flight takes no packets, as in sgpu_frames_recv)
-            if (d && BD(d)->core.ge_pending())
-                d = nullptr;
-            if (d && h.type == kFrameOriginal) {
-                SiameseOriginalPacket p;
-                p.PacketNum = h.packetNum;
-                p.Data = reinterpret_cast<const unsigned char*>((uintptr_t)data);
-                p.DataBytes = h.dataBytes;
-                r = BD(d)->core.add_original(p, data);
-                ++accepted;
-            } else if (d) {
-                RowMeta m;
-                const uint8_t* tail = h.tail + 8 - h.tailBytes;
-                const int footer = read_footer(tail, h.tailBytes, &m);
-                if (footer > 0 && (unsigned)footer < h.dataBytes) {
-                    DeviceRecovery rec;
-                    rec.data = data;
-                    rec.bytes = h.dataBytes;
-                    rec.footer = h.tail + 8 - footer;
-                    rec.footerBytes = (unsigned)footer;
-                    rec.head = h.head;
-                    rec.producer = nullptr;   // ingested from the row, any alignment
-                    r = BD(d)->core.add_recovery_device(rec);
-                    ++accepted;
-                }
-            }
-        }
+        else if (row_head_valid(h, stride))
+            r = route_head(decoders, decoderCount, h, dev + (uint64_t)k * stride + h.headerBytes, &accepted);
         if (results)
             results[k] = r;
         if (r != Siamese_Success && r != Siamese_NeedMoreData && status == Siamese_Success)
@@ -705,6 +726,99 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_rows(const SgpuDecoder* decoders, 
     }
     *acceptedOut = accepted;
     return status;
+}
+
+SIAMESE_EXPORT size_t sgpu_frames_packed_bytes(unsigned count, unsigned maxFrames)
+{
+    return maxFrames >= 1 && maxFrames <= kPackedMaxFrames ? (size_t)packed_bytes(count, maxFrames) : 0;
+}
+
+SIAMESE_EXPORT long long sgpu_frames_scan_packed(const void* deviceRows, size_t stride, const unsigned* deviceLens,
+                                                 unsigned count, unsigned maxFrames, void* pinnedOut)
+{
+    if (!g_batchReady || !rows_ok(deviceRows, stride, count) || ((uintptr_t)deviceLens & 3) ||
+        ((uintptr_t)pinnedOut & 15) || (!pinnedOut && count > 0) || maxFrames < 1 || maxFrames > kPackedMaxFrames ||
+        packed_bytes(count, maxFrames) > ((uint64_t)1 << 32))
+        return -1;
+    return (long long)Engine::global()->walk_rows_async(deviceRows, stride, deviceLens, count, maxFrames, pinnedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_packed(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                     const void* heads, unsigned maxFrames, const void* deviceRows,
+                                                     size_t stride, unsigned count, SiameseResult* results,
+                                                     unsigned* acceptedOut)
+{
+    if (!acceptedOut)
+        return Siamese_InvalidInput;
+    *acceptedOut = 0;
+    if (!rows_ok(deviceRows, stride, count) || ((!decoders || !heads) && count > 0) || ((uintptr_t)heads & 3) ||
+        maxFrames < 1 || maxFrames > kPackedMaxFrames)
+        return Siamese_InvalidInput;
+    const uint64_t dev = (uint64_t)(uintptr_t)deviceRows;
+    const uint8_t* recs = static_cast<const uint8_t*>(heads);
+    const uint8_t* words = recs + (size_t)count * maxFrames * sizeof(PackedHead);
+    unsigned accepted = 0;
+    SiameseResult status = Siamese_Success;
+    for (unsigned k = 0; k < count; ++k) {
+        // (the words and records are the caller's memory: each is copied, checked and only then used)
+        uint32_t word;
+        std::memcpy(&word, words + (size_t)k * 4, 4);
+        SiameseResult* res = results ? results + (size_t)k * maxFrames : nullptr;
+        for (unsigned j = 0; res && j < maxFrames; ++j)
+            res[j] = Siamese_NeedMoreData;
+        unsigned n = word & kPackedCountMask;
+        bool malformed = (word & kPackedMalformed) != 0;
+        if (n > maxFrames) {   // (no scan writes such a word: none of the row's records is used)
+            n = 0;
+            malformed = true;
+        }
+        for (unsigned j = 0; j < n; ++j) {
+            PackedHead h;
+            std::memcpy(&h, recs + ((size_t)k * maxFrames + j) * sizeof(h), sizeof(h));
+            SiameseResult r = Siamese_InvalidInput;
+            if (packed_head_valid(h, stride))
+                r = route_head(decoders, decoderCount, h, dev + (uint64_t)k * stride + h.offset + h.headerBytes,
+                               &accepted);
+            if (res)
+                res[j] = r;
+            if (r != Siamese_Success && r != Siamese_NeedMoreData && status == Siamese_Success)
+                status = r;
+        }
+        if (malformed) {   // the frame the walk stopped at: the slot after the row's last record, if there is one
+            if (res && n < maxFrames)
+                res[n] = Siamese_InvalidInput;
+            if (status == Siamese_Success)
+                status = Siamese_InvalidInput;
+        }
+    }
+    *acceptedOut = accepted;
+    return status;
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_encoder_pack_frames(SgpuEncoder encoder, unsigned flow, unsigned firstPacketNum,
+                                                      unsigned originalCount, const SgpuRecoveryPacket* recovery,
+                                                      unsigned recoveryCount, void* deviceDst, size_t stride,
+                                                      unsigned maxRows, unsigned* deviceLens, SiameseResult* results,
+                                                      unsigned* rowsOut, unsigned* framesOut)
+{
+    if (rowsOut)
+        *rowsOut = 0;
+    if (framesOut)
+        *framesOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, lens = (uint64_t)(uintptr_t)deviceLens;
+    if (!encoder || !rowsOut || !framesOut || !frame_rows_ok(maxRows, dst, stride, lens) || flow > kFrameMaxFlow ||
+        firstPacketNum > SIAMESE_PACKET_NUM_MAX || (!recovery && recoveryCount))
+        return Siamese_InvalidInput;
+    EncoderCore& core = BE(encoder)->core;
+    std::vector<EncoderCore::PackRecovery> rec(recoveryCount);
+    for (unsigned k = 0; k < recoveryCount; ++k) {
+        if (recovery[k].Producer != &core.program())
+            return Siamese_InvalidInput;
+        rec[k].data = (uint64_t)(uintptr_t)recovery[k].DeviceData;
+        rec[k].bytes = recovery[k].DataBytes;
+    }
+    return core.pack_frames(flow, firstPacketNum, originalCount, rec.data(), recoveryCount, dst, (uint64_t)stride,
+                            maxRows, lens, results, rowsOut, framesOut);
 }
 
 SIAMESE_EXPORT long long sgpu_frames_send(unsigned count, const SgpuRecoveryPacket* packets, const unsigned* flows,
@@ -755,13 +869,13 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[24] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[25] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
                             s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide,
-                            s.delivers,   s.frames,      s.scans};
-    for (unsigned k = 0; k < count && k < 24; ++k)
+                            s.delivers,   s.frames,      s.scans,      Engine::global()->walks()};
+    for (unsigned k = 0; k < count && k < 25; ++k)
         out[k] = v[k];
 }
 

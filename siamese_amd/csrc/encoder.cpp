@@ -448,6 +448,94 @@ SiameseResult EncoderCore::deliver_range(unsigned firstNum, unsigned count, unsi
     return Siamese_Success;
 }
 
+SiameseResult EncoderCore::pack_frames(unsigned flow, unsigned firstNum, unsigned originalCount,
+                                       const PackRecovery* rec, unsigned recCount, uint64_t dst, uint64_t stride,
+                                       unsigned maxRows, uint64_t lens, SiameseResult* results, unsigned* rows,
+                                       unsigned* frames)
+{
+    *rows = *frames = 0;
+    if (dead())
+        return Siamese_Disabled;
+    struct Placed
+    {
+        uint64_t src;
+        uint32_t bytes, hdrLen, column;
+        uint64_t row, off;
+        uint8_t hdr[kFrameMaxHeader];
+    };
+    std::vector<Placed> placed;
+    placed.reserve((size_t)originalCount + recCount);
+    uint64_t row = 0, off = 0;
+    // the layout rule (encoder.h); false: the frame is longer than a row
+    auto place = [&](unsigned type, unsigned column, uint64_t src, uint32_t n) {
+        Placed p;
+        std::memset(p.hdr, 0, sizeof(p.hdr));
+        p.src = src;
+        p.bytes = n;
+        p.column = column;
+        p.hdrLen = frame_write_header(type, flow, column, n, p.hdr);
+        const uint64_t T = (uint64_t)p.hdrLen + n;
+        if (T > stride)
+            return false;
+        if (off + T > stride) {
+            ++row;
+            off = 0;
+        }
+        p.row = row;
+        p.off = off;
+        off = (off + T + 15) & ~(uint64_t)15;
+        placed.push_back(p);
+        return true;
+    };
+    for (unsigned k = 0; k < originalCount; ++k) {
+        // the unacknowledged window, as deliver_range() sees it
+        const unsigned column = column_add(firstNum, k);
+        const unsigned e = column_to_element(column);
+        if (e >= count_ || e < firstUnremoved_)
+            continue;
+        const EncSlot& s = slot(e);
+        if (s.bytes == 0 || s.column != column)
+            continue;
+        if (!place(kFrameOriginal, column, s.buf.addr() + s.header, s.bytes - s.header))
+            return Siamese_InvalidInput;
+    }
+    const size_t originals = placed.size();
+    for (unsigned k = 0; k < recCount; ++k) {
+        bool mine = rec[k].data != 0 && recovery_ && rec[k].data == recovery_.addr();
+        for (const DevBuf& b : recoveryHeld_)
+            mine = mine || (rec[k].data != 0 && b && rec[k].data == b.addr());
+        if (!mine || rec[k].bytes == 0 || rec[k].bytes > SIAMESE_MAX_PACKET_BYTES ||
+            !place(kFrameRecovery, 0, rec[k].data, rec[k].bytes))
+            return Siamese_InvalidInput;
+    }
+    const uint64_t need = placed.empty() ? 0 : row + 1;
+    if (need > maxRows) {
+        *rows = (unsigned)std::min<uint64_t>(need, 0xffffffffu);
+        return Siamese_InvalidInput;
+    }
+    if (results) {
+        size_t i = 0;
+        for (unsigned k = 0; k < originalCount; ++k) {
+            const bool present = i < originals && placed[i].column == column_add(firstNum, k);
+            results[k] = present ? Siamese_Success : Siamese_NeedMoreData;
+            i += present;
+        }
+    }
+    for (size_t i = 0; i < placed.size(); ++i) {
+        const Placed& p = placed[i];
+        const bool last = i + 1 == placed.size() || placed[i + 1].row != p.row;
+        const uint64_t span = (last ? stride : placed[i + 1].off) - p.off;
+        prog_.frame(p.src, p.bytes, p.hdr, p.hdrLen, dst + p.row * stride + p.off, last ? lens + p.row * 4 : 0, span,
+                    last ? (uint32_t)p.off : 0);
+    }
+    const uint8_t none[kFrameMaxHeader] = {};
+    for (uint64_t r = need; r < maxRows; ++r)   // rows not used: only a zero length
+        prog_.frame(0, 0, none, 0, dst + r * stride, lens + r * 4, stride);
+    *rows = (unsigned)need;
+    *frames = (unsigned)placed.size();
+    return Siamese_Success;
+}
+
 // ---------------------------------------------------------------------------
 // Encode
 

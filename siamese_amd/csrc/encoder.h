@@ -122,6 +122,29 @@ public:
     static constexpr unsigned kFrameNone = 0xffffffffu;
     SiameseResult deliver_range(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst, uint64_t stride,
                                 uint64_t lens, SiameseResult* results, unsigned* queued);
+    /// sgpu_encoder_pack_frames: queue the present originals firstNum, firstNum
+    /// + 1, ... (originalCount of them, ascending) and then the recovery
+    /// packets rec[0, recCount) as frames for `flow`, several to a row of
+    /// `stride` bytes at dst + row * stride.  The layout rule: a cursor (row,
+    /// off) from (0, 0); a frame of T = header + data bytes with off + T >
+    /// stride moves to (row + 1, 0); it is placed at off, then off =
+    /// align16(off + T).  One Program::frame item per frame covers its slot
+    /// (to the next frame of the row, the row's last to the row's end: rows are
+    /// written whole); the last item of a row also writes the row's length
+    /// word lens + 4 row = its offset + T (FrameItem::lenBase), and rows
+    /// [*rows, maxRows) get a length-only item (zero).  An absent original
+    /// takes no space (results[k] = NeedMoreData).  Never waits.
+    /// InvalidInput, with nothing queued: a frame with T > stride, a recovery
+    /// packet that is not among this encoder's current output, or more rows
+    /// than maxRows (*rows = the rows needed).
+    struct PackRecovery
+    {
+        uint64_t data;
+        uint32_t bytes;
+    };
+    SiameseResult pack_frames(unsigned flow, unsigned firstNum, unsigned originalCount, const PackRecovery* rec,
+                              unsigned recCount, uint64_t dst, uint64_t stride, unsigned maxRows, uint64_t lens,
+                              SiameseResult* results, unsigned* rows, unsigned* frames);
     /// Generate the next recovery packet (device ops queued, not flushed).
     SiameseResult encode(EncodeOut& out);
     /// `count` encode() calls in one (sgpu_encode_range): out[k] as the k-th

@@ -889,7 +889,7 @@ void Program::deliver(uint64_t src, uint32_t cap, uint64_t dst, uint64_t lenOut,
 }
 
 void Program::frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t hdrLen, uint64_t dst,
-                    uint64_t lenOut, uint64_t stride)
+                    uint64_t lenOut, uint64_t stride, uint32_t lenBase)
 {
     touch();
     FrameItem it;
@@ -901,7 +901,7 @@ void Program::frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t h
     std::memset(it.hdr, 0, sizeof(it.hdr));
     std::memcpy(it.hdr, hdr, hdrLen);
     it.hdrLen = (uint8_t)hdrLen;
-    it.pad = 0;
+    it.lenBase = lenBase;
     if (b_->nframe == b_->frames.size())
         b_->frames.emplace_back();
     b_->frames[b_->nframe++] = it;
@@ -2932,8 +2932,9 @@ int64_t Engine::gather_async_framed(unsigned count, const void* const* srcs, con
     return ticket;
 }
 
-int64_t Engine::scan_rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
-                                void* pinnedOut)
+// scan_rows_async (maxFrames == 0: k_scan) and walk_rows_async (k_walk)
+int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
+                           unsigned maxFrames, void* pinnedOut)
 {
     if (failed())
         return -1;
@@ -2945,7 +2946,7 @@ int64_t Engine::scan_rows_async(const void* rows, uint64_t stride, const uint32_
     if (!gather_land(g))   // (the slot's previous gather, kGatherSlots back)
         return -1;
     // the records take the slot's packing area; a scan uploads no descriptors
-    const size_t total = (size_t)count * sizeof(RowHead);
+    const size_t total = maxFrames ? (size_t)packed_bytes(count, maxFrames) : (size_t)count * sizeof(RowHead);
     if (total > g.stageCap) {
         size_t c = g.stageCap ? g.stageCap : (1u << 20);
         while (c < total)
@@ -2958,12 +2959,15 @@ int64_t Engine::scan_rows_async(const void* rows, uint64_t stride, const uint32_
     if (!g.stage)
         return -1;
     void* packed = nullptr;
-    if (!be_scan_rows(rows, stride, lens, count, g.stage, pinnedOut, &packed, &g.landed)) {
+    if (!(maxFrames ? be_walk_rows(rows, stride, lens, count, maxFrames, g.stage, pinnedOut, &packed, &g.landed)
+                    : be_scan_rows(rows, stride, lens, count, g.stage, pinnedOut, &packed, &g.landed))) {
         failed_.store(true, std::memory_order_relaxed);
         return -1;
     }
     g.ticket = ticket;
-    {
+    if (maxFrames)
+        walks_.fetch_add(count, std::memory_order_relaxed);
+    else {
         std::lock_guard<std::mutex> s(statsMu_);
         flushStats_.scans += count;
     }

@@ -526,12 +526,13 @@ public:
     /// Queue a frame item (ops.h FrameItem): hdrLen (<= kFrameMaxHeader)
     /// literal header bytes, then `bytes` from src (any alignment; 0: an absent
     /// packet) into the caller's row dst[0, stride), hdrLen + bytes <= stride,
-    /// the sum at lenOut.  Ordered as deliver()'s items: one launch after the
+    /// lenBase plus the sum at lenOut (0: no length word; FrameItem says what
+    /// a packed row's items pass).  Ordered as deliver()'s items: one launch after the
     /// submission's last executor / solve launch, so a recovery packet encoded
     /// in the same submission is framed from its final bytes.  A program whose
     /// only work is framing still makes a submission.
     void frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t hdrLen, uint64_t dst, uint64_t lenOut,
-               uint64_t stride);
+               uint64_t stride, uint32_t lenBase = 0);
 
     bool empty() const { return !b_ || b_->empty(); }
 
@@ -680,7 +681,18 @@ public:
     /// device memory, or null.  The rows are read before any later
     /// submission's device work, as a gather's sources are.
     int64_t scan_rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
-                            void* pinnedOut);
+                            void* pinnedOut)
+    {
+        return rows_async(rows, stride, lens, count, 0, pinnedOut);
+    }
+    /// The same for rows that hold several frames: maxFrames (1 .. kPackedMaxFrames)
+    /// PackedHead records per row and then the row words, packed_bytes(count,
+    /// maxFrames) in all, into pinnedOut (k_walk, sgpu_frames_scan_packed).
+    int64_t walk_rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
+                            unsigned maxFrames, void* pinnedOut)
+    {
+        return rows_async(rows, stride, lens, count, maxFrames, pinnedOut);
+    }
     /// Wait until gather `ticket` and every earlier one have landed.
     bool gather_wait(int64_t ticket);
     /// Host -> device copy on the staging stream, issued now; every later
@@ -853,6 +865,14 @@ private:
     } gslots_[kGatherSlots];
     int64_t gNext_ = 0;
     bool gather_land(GatherSlot& g);
+    int64_t rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count, unsigned maxFrames,
+                       void* pinnedOut);
+    // rows scanned by the packed scan, counted when the scan is queued (sgpu_engine_stats_ex [24]); kept
+    // here, behind every other member, and not in EngineStats, whose size every submission's counters share
+    std::atomic<uint64_t> walks_{0};
+
+public:
+    uint64_t walks() const { return walks_.load(std::memory_order_relaxed); }
 };
 
 /// Per-host-thread engine state.  Only its owning thread touches it between

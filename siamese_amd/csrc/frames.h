@@ -125,4 +125,85 @@ inline void row_head_scan(const uint8_t* row, uint64_t stride, const uint32_t* l
     *out = r;
 }
 
+/// Rows that hold several frames (ops.h PackedHead, sgpu_frames_scan_packed /
+/// sgpu_frames_recv_packed).  row_head_valid restated for a frame at an
+/// offset: the same checks, with offset + headerBytes + dataBytes within the
+/// stride.  sgpu_frames_recv_packed acts on no record that fails it.
+inline bool packed_head_valid(const PackedHead& r, uint64_t stride)
+{
+    if (r.status != kRowOk || r.type > kFrameRecovery)
+        return false;
+    const unsigned inner = r.type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+    if (r.dataBytes < 1 || r.dataBytes > SIAMESE_MAX_PACKET_BYTES)
+        return false;
+    if (r.headerBytes < inner + 1 || r.headerBytes > inner + 4)
+        return false;
+    if ((uint64_t)r.offset + r.headerBytes + r.dataBytes > stride)
+        return false;
+    if (r.flow > kFrameMaxFlow)
+        return false;
+    if (r.type == kFrameOriginal)
+        return r.packetNum <= SIAMESE_PACKET_NUM_MAX && r.tailBytes == 0;
+    return r.tailBytes == (r.dataBytes < 8 ? r.dataBytes : 8u);
+}
+
+/// What k_walk computes for one row: row[0, stride) in host memory, len = the
+/// row's length word or null, out = the row's maxFrames records.  With
+/// end = len ? *len : stride: end == 0 is an empty row and end > stride a
+/// malformed one without records.  Otherwise row[0, end) is walked as
+/// frames_parse walks it: a zero byte where a frame would start is skipped,
+/// the prefix is read from the bytes left before end, and a frame is accepted
+/// when frames_parse accepts it and packed_head_valid does (which adds the
+/// PacketNum range).  The first frame that is not accepted ends the walk with
+/// kPackedMalformed; after maxFrames records it ends with kPackedMore if a
+/// non-zero byte is left before end.  Records past the last accepted frame
+/// are zero.  Returns the row word.
+inline uint32_t row_walk(const uint8_t* row, uint64_t stride, const uint32_t* len, uint32_t maxFrames,
+                         PackedHead* out)
+{
+    std::memset(out, 0, (size_t)maxFrames * sizeof(*out));
+    const uint64_t end = len ? *len : stride;
+    if (end > stride)
+        return kPackedMalformed;
+    uint64_t at = 0;
+    uint32_t n = 0;
+    while (at < end) {
+        if (row[at] == 0) {
+            ++at;
+            continue;
+        }
+        if (n == maxFrames)
+            return n | kPackedMore;
+        const uint64_t left = end - at;
+        unsigned length = 0;
+        const int h = read_length_prefix(row + at, left < 4 ? (unsigned)left : 4u, &length);
+        if (h < 1 || length < 1 || (uint64_t)h + length > left)
+            return n | kPackedMalformed;
+        const uint8_t* f = row + at + h;   // type, flow, PacketNum: before end when L > inner
+        PackedHead r;
+        std::memset(&r, 0, sizeof(r));
+        r.offset = (uint32_t)at;
+        r.status = kRowOk;
+        r.type = f[0];
+        const unsigned inner = r.type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+        if (r.type > kFrameRecovery || length <= inner)
+            return n | kPackedMalformed;
+        r.headerBytes = (uint8_t)(h + inner);
+        r.flow = f[1] | ((uint32_t)f[2] << 8) | ((uint32_t)f[3] << 16);
+        r.packetNum = r.type == kFrameOriginal ? f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) : 0;
+        r.dataBytes = length - inner;
+        r.tailBytes = r.type == kFrameRecovery ? (uint8_t)(r.dataBytes < 8 ? r.dataBytes : 8) : 0;
+        if (!packed_head_valid(r, end))
+            return n | kPackedMalformed;
+        if (r.type == kFrameRecovery) {
+            const uint8_t* data = row + at + r.headerBytes;
+            std::memcpy(r.head, data, r.dataBytes < 4 ? r.dataBytes : 4);
+            std::memcpy(r.tail + 8 - r.tailBytes, data + r.dataBytes - r.tailBytes, r.tailBytes);
+        }
+        out[n++] = r;
+        at += (uint64_t)h + length;
+    }
+    return n;
+}
+
 } // namespace sgpu

@@ -418,10 +418,13 @@ constexpr uint32_t kDeliverMaxChunks = 4096;
 /// One sender packet framed into a caller-owned device row (k_frame,
 /// sgpu_frames_deliver_recovery / sgpu_encoder_deliver_range).  With
 /// T = hdrLen + bytes:  dst[0, hdrLen) = hdr, dst[hdrLen, T) = src[0, bytes),
-/// dst[T, stride) = 0 and *lenOut = T (the host guarantees T <= stride).  src
+/// dst[T, stride) = 0 and *lenOut = lenBase + T (the host guarantees T <= stride).  src
 /// has any byte alignment (a recovery packet's arena buffer, or an original's
 /// slot address plus its prefix bytes); src = 0: an absent packet, only
-/// *lenOut = 0 is written.  Only aligned 16-byte words holding a byte of
+/// *lenOut = lenBase is written.  lenOut = 0: no length word is written (a
+/// frame that is not the last of a packed row, sgpu_encoder_pack_frames, where
+/// dst is the frame's slot in the row, stride16 the slot's span and lenBase the
+/// slot's offset in the row).  Only aligned 16-byte words holding a byte of
 /// [src, src + bytes) are read, nothing outside [dst, dst + stride) and the
 /// length word is written.  hdr is the literal frame header (frames.h: an
 /// original's is prefix <= 4 plus 7 bytes), hdrLen = 0 for a bare packet.  The
@@ -431,12 +434,12 @@ struct FrameItem
 {
     uint64_t src;        // the packet's first byte (0: absent)
     uint64_t dst;        // the row, 16-byte aligned
-    uint64_t lenOut;     // uint32 length word, 4-byte aligned
+    uint64_t lenOut;     // uint32 length word, 4-byte aligned (0: none)
     uint32_t bytes;      // packet bytes after the header
     uint32_t stride16;   // the row's bytes / 16 (1 .. 2^28)
     uint8_t hdr[kFrameMaxHeader];
     uint8_t hdrLen;
-    uint32_t pad;
+    uint32_t lenBase;    // added to the length word (0 but for a packed row's last frame)
 };
 static_assert(sizeof(FrameItem) == 48, "FrameItem layout");
 /// k_frame's grid is k_deliver's: kDeliverWaves items per workgroup, at most
@@ -473,6 +476,40 @@ struct RowHead
 static_assert(sizeof(RowHead) == 32, "RowHead layout");
 /// k_scan: one lane per row, kScanThreads rows per workgroup.
 constexpr uint32_t kScanThreads = 256;
+
+/// One frame of a row that holds several (k_walk, sgpu_frames_scan_packed):
+/// the layout of SgpuPackedHead, RowHead with the frame's offset in the row in
+/// place of frameBytes; the data is at offset + headerBytes.  Row k of a scan
+/// with maxFrames records per row owns records [k * maxFrames, (k + 1) *
+/// maxFrames) and, after all records, row word k: the number of records that
+/// are kRowOk (the row's first ones; the rest are zero) with kPackedMore when
+/// a non-zero byte is left after maxFrames frames and kPackedMalformed when
+/// the walk stopped at a frame it could not accept (frames.h row_walk states
+/// the walk).  Nothing outside [row, row + stride) and the row's length word
+/// is read.
+struct PackedHead
+{
+    uint32_t offset;       // of the frame's length prefix in the row
+    uint8_t status;        // kRowEmpty / kRowOk
+    uint8_t type;
+    uint8_t headerBytes;   // prefix + inner header (<= kFrameMaxHeader)
+    uint8_t tailBytes;
+    uint32_t flow;
+    uint32_t packetNum;
+    uint32_t dataBytes;
+    uint8_t head[4];
+    uint8_t tail[8];
+};
+static_assert(sizeof(PackedHead) == 32, "PackedHead layout");
+constexpr uint32_t kPackedMore = 0x80000000u, kPackedMalformed = 0x40000000u, kPackedCountMask = 0xffffu;
+constexpr uint32_t kPackedMaxFrames = 256;
+/// k_walk: one lane per row, kWalkThreads rows per workgroup.
+constexpr uint32_t kWalkThreads = 256;
+/// Bytes of a packed scan's output: the records, then the row words.
+constexpr uint64_t packed_bytes(uint64_t count, uint64_t maxFrames)
+{
+    return count * maxFrames * sizeof(PackedHead) + count * 4;
+}
 
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)

@@ -477,8 +477,8 @@ void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t)
 }
 
 // k_frame (ops.h FrameItem): the literal header, the packet and a zero tail
-// into the row, the sum of the first two in the length word; an absent packet
-// only its zero length word.
+// into the row, lenBase plus the sum of the first two in the length word when
+// the item has one; an absent packet only its length word.
 void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t)
 {
     if (noexec())
@@ -487,8 +487,9 @@ void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t)
         const FrameItem& it = items[i];
         const uint64_t stride = (uint64_t)it.stride16 << 4;
         const uint64_t total = it.src != 0 ? (uint64_t)it.hdrLen + it.bytes : 0;
-        const uint32_t lw = (uint32_t)total;
-        std::memcpy(P(it.lenOut), &lw, 4);
+        const uint32_t lw = it.lenBase + (uint32_t)total;
+        if (it.lenOut != 0)
+            std::memcpy(P(it.lenOut), &lw, 4);
         if (it.src == 0)
             continue;
         for (uint64_t b = 0; b < stride; ++b)
@@ -646,6 +647,23 @@ bool be_scan_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint3
         row_head_scan(static_cast<const uint8_t*>(rows) + (uint64_t)k * stride, stride, lens ? lens + k : nullptr,
                       out + k);
     std::memcpy(hostOut, devStage, (size_t)count * sizeof(RowHead));
+    return true;
+}
+
+// k_walk (ops.h PackedHead): frames.h row_walk per row, the row words after
+// the records.
+bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                  void* devStage, void* hostOut, void** packed, void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    PackedHead* out = static_cast<PackedHead*>(devStage);
+    uint8_t* words = static_cast<uint8_t*>(devStage) + (size_t)count * maxFrames * sizeof(PackedHead);
+    for (uint32_t k = 0; k < count; ++k) {
+        const uint32_t w = row_walk(static_cast<const uint8_t*>(rows) + (uint64_t)k * stride, stride,
+                                    lens ? lens + k : nullptr, maxFrames, out + (size_t)k * maxFrames);
+        std::memcpy(words + (size_t)k * 4, &w, 4);
+    }
+    std::memcpy(hostOut, devStage, (size_t)packed_bytes(count, maxFrames));
     return true;
 }
 

@@ -133,6 +133,15 @@ bool be_scan_rows(const void*, uint64_t, const uint32_t*, uint32_t count, void* 
     return true;
 }
 
+bool be_walk_rows(const void*, uint64_t, const uint32_t*, uint32_t count, uint32_t maxFrames, void* devStage,
+                  void* hostOut, void** packed, void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    std::memset(devStage, 0, (size_t)packed_bytes(count, maxFrames));
+    std::memcpy(hostOut, devStage, (size_t)packed_bytes(count, maxFrames));
+    return true;
+}
+
 bool be_sync() { return true; }
 void* be_fence() { return reinterpret_cast<void*>(1); }
 bool be_fence_wait(void*, unsigned, bool) { return true; }

@@ -1,0 +1,197 @@
+#!/usr/bin/env python3
+"""sgpu_frames_scan_packed against the copy it replaces and the one-frame scan.
+
+The scan probe's row count (tools/scan_probe.py): 1024 flows x 320 rows =
+327,680 rows of 1424 B in device memory, but every row holds eight frames
+(seven originals of 160 B and a recovery packet of 170 B, each frame at a
+16-byte boundary, as sgpu_encoder_pack_frames lays them out).  Three ways to
+look at them, timed in the same process, interleaved, after a warm-up:
+
+  (a) sgpu_frames_scan_packed (maxFrames 8) + sgpu_gather_wait: k_walk writes
+      eight 32-byte records and a word per row, one DMA brings them to pinned
+      memory (host wall clock around both calls; the kernel's own device time
+      is sgpu_timing_kernels[8]);
+  (b) what sgpu_frames_recv needs: a device-to-host copy of every row into
+      pinned memory (hipMemcpyAsync of the HIP runtime the library itself
+      loaded, host wall clock until the copy's event has passed);
+  (c) sgpu_frames_scan_rows + sgpu_gather_wait on the same buffer: the
+      one-frame scan, which sees the first frame of each row only, as the
+      floor (its kernel time is sgpu_timing_kernels[7]).
+
+The medians are reported, with every repetition.
+
+    python tools/pack_probe.py [--flows 1024] [--rows 320] [--frames 8] [--reps 9] [--out FILE]
+
+Needs an MI355X: without one the library refuses to initialise and the probe
+fails (no CPU fallback; --library with the CPU test double rehearses the call
+sequence only and prints no time).
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HIP_D2H = 2   # hipMemcpyDeviceToHost
+
+
+def hip_runtime():
+    """The HIP runtime already in the process (the library's own)."""
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libamdhip64" in line:
+                return C.CDLL(line.split()[-1])
+    sys.exit("pack_probe: no HIP runtime in the process")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--library", default=os.path.join(ROOT, "siamese_amd", "libsiamese_amd.so"))
+    ap.add_argument("--flows", type=int, default=1024)
+    ap.add_argument("--rows", type=int, default=320, help="rows per flow")
+    ap.add_argument("--frames", type=int, default=8, help="frames per row: the last is a recovery packet")
+    ap.add_argument("--bytes", type=int, default=160)
+    ap.add_argument("--stride", type=int, default=1424)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    a = ap.parse_args()
+    rehearsal = "hostsim" in os.path.basename(a.library)
+
+    from siamese_amd.binding import ROW_OK, PackedHead, RowHead, bind_packed_abi
+    L = bind_packed_abi(C.CDLL(a.library))
+    L.sgpu_device_alloc.restype = C.c_void_p
+    L.sgpu_device_alloc.argtypes = [C.c_size_t]
+    L.sgpu_host_alloc.restype = C.c_void_p
+    L.sgpu_host_alloc.argtypes = [C.c_size_t]
+    L.sgpu_h2d.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sgpu_frame_write_header.restype = C.c_uint
+    L.sgpu_frame_write_header.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
+    L.sgpu_timing.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.sgpu_timing_kernels.argtypes = [C.c_void_p, C.c_uint]
+    if L.sgpu_init(-1 if rehearsal else 0) != 0:
+        sys.exit("pack_probe: the library did not initialise (no MI355X?)")
+
+    n, per, nf, size, stride = a.flows, a.rows, a.frames, a.bytes, a.stride
+    rows = n * per
+    total = rows * stride
+    rsize = size + 10
+
+    def header(kind, flow, num, nbytes):
+        out = (C.c_ubyte * 16)()
+        return bytes(out[:L.sgpu_frame_write_header(kind, flow, num, nbytes, out)])
+
+    # one flow's rows at a time: row r holds originals r*(nf-1) .. and a
+    # recovery packet (a stand-in of the right size: the scan reads its ends,
+    # not its sense), every frame at a 16-byte boundary
+    rng = random.Random(7)
+    data = [rng.randbytes(rsize) for _ in range(nf)]
+    dev = L.sgpu_device_alloc(total)
+    lens = L.sgpu_device_alloc(4 * rows)
+    assert dev and lens
+    for i in range(n):
+        block, lw = [], []
+        for r in range(per):
+            row = bytearray()
+            for j in range(nf):
+                row += bytes(-len(row) % 16)
+                row += (header(0, i, r * (nf - 1) + j, size) + data[j][:size]) if j < nf - 1 else \
+                    (header(1, i, 0, rsize) + data[j])
+            assert len(row) <= stride
+            lw.append(len(row).to_bytes(4, "little"))
+            block.append(bytes(row) + bytes(stride - len(row)))
+        blob, lraw = b"".join(block), b"".join(lw)
+        assert L.sgpu_h2d(dev + i * per * stride, blob, len(blob)) == 0
+        assert L.sgpu_h2d(lens + 4 * i * per, lraw, len(lraw)) == 0
+
+    outBytes = L.sgpu_frames_packed_bytes(rows, nf)
+    packed = L.sgpu_host_alloc(outBytes)
+    heads = L.sgpu_host_alloc(rows * C.sizeof(RowHead))
+    assert packed and heads
+    if not rehearsal:
+        hip = hip_runtime()
+        host = L.sgpu_host_alloc(total)
+        assert host
+        ev = C.c_void_p()
+        assert hip.hipEventCreate(C.byref(ev)) == 0
+
+    def timed(call, index):
+        L.sgpu_timing(1, 1, None, None)
+        t0 = time.perf_counter()
+        t = call()
+        assert t > 0 and L.sgpu_gather_wait(t) == 0
+        wall = (time.perf_counter() - t0) * 1e3
+        ms = (C.c_double * 9)()
+        L.sgpu_timing_kernels(ms, 9)
+        return wall, ms[index]
+
+    def walk_ms():
+        return timed(lambda: L.sgpu_frames_scan_packed(dev, stride, lens, rows, nf, packed), 8)
+
+    def scan_ms():
+        return timed(lambda: L.sgpu_frames_scan_rows(dev, stride, None, rows, heads), 7)
+
+    def copy_ms():
+        t0 = time.perf_counter()
+        ok = (hip.hipMemcpyAsync(C.c_void_p(host), C.c_void_p(dev), C.c_size_t(total), HIP_D2H, None) == 0 and
+              hip.hipEventRecord(ev, None) == 0 and hip.hipEventSynchronize(ev) == 0)
+        wall = (time.perf_counter() - t0) * 1e3
+        assert ok, "the device-to-host copy failed"
+        return wall
+
+    wk, wn, sc, kn, cp = [], [], [], [], []
+    for r in range(a.warmup + a.reps):
+        w, wkn = walk_ms()
+        c = copy_ms() if not rehearsal else 0.0
+        s, k = scan_ms()
+        if r >= a.warmup:
+            wk.append(w)
+            wn.append(wkn)
+            sc.append(s)
+            kn.append(k)
+            cp.append(c)
+    L.sgpu_timing(0, 1, None, None)
+
+    # spot check: first and last flow, first and last row, every frame
+    recs = (PackedHead * (rows * nf)).from_address(packed)
+    words = (C.c_uint * rows).from_address(packed + rows * nf * C.sizeof(PackedHead))
+    for i in (0, n - 1):
+        for r in (0, per - 1):
+            k = i * per + r
+            assert words[k] == nf, "row %d: word %#x" % (k, words[k])
+            for j in range(nf):
+                h = recs[k * nf + j]
+                want = (size, 0, r * (nf - 1) + j) if j < nf - 1 else (rsize, 1, 0)
+                assert (h.Status, h.Flow, h.DataBytes, h.Type, h.PacketNum) == (ROW_OK, i) + want, "row %d frame %d" % (k, j)
+                assert h.Offset % 16 == 0
+                if j == nf - 1:
+                    assert bytes(h.Tail) == data[j][-8:] and bytes(h.Head) == data[j][:4]
+
+    out = {"probe": "pack", "flows": n, "rows_per_flow": per, "frames_per_row": nf, "bytes": size, "stride": stride,
+           "reps": a.reps, "rows": rows, "frames": rows * nf, "output_bytes": outBytes, "row_bytes": total}
+    if not rehearsal:
+        med = statistics.median
+        out.update({"walk_wait_ms_median": round(med(wk), 4), "walk_wait_ms": [round(v, 4) for v in wk],
+                    "k_walk_ms_median": round(med(wn), 4), "k_walk_ms": [round(v, 4) for v in wn],
+                    "copy_rows_ms_median": round(med(cp), 4), "copy_rows_ms": [round(v, 4) for v in cp],
+                    "scan_rows_wait_ms_median": round(med(sc), 4), "scan_rows_wait_ms": [round(v, 4) for v in sc],
+                    "k_scan_ms_median": round(med(kn), 4), "k_scan_ms": [round(v, 4) for v in kn],
+                    "copy_over_walk": round(med(cp) / med(wk), 2), "walk_over_scan_rows": round(med(wk) / med(sc), 2),
+                    "k_walk_frames_per_us": round(rows * nf / (med(wn) * 1e3), 1) if med(wn) else None})
+    else:
+        out["rehearsal"] = "CPU test double: call sequence only, no time"
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
