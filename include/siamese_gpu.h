@@ -201,6 +201,45 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_range(SgpuDecoder decoder, uns
                                                         void* deviceDst, size_t stride, unsigned* deviceLens,
                                                         SiameseResult* results /* host, optional */,
                                                         unsigned* queuedOut);
+/// sgpu_decoder_deliver_range with each present packet written as a wire frame
+/// ("Framed datagrams" below): what a decode-and-forward relay sends on.  For
+/// packet k of n payload bytes, with h = sgpu_frame_header_bytes(
+/// SGPU_FRAME_ORIGINAL, n): bytes [0, h) of row k are what
+/// sgpu_frame_write_header(SGPU_FRAME_ORIGINAL, flow, packetNum_k, n, ...)
+/// writes, bytes [h, h + n) the payload, bytes [h + n, stride) zero, and
+/// deviceLens[k] = h + n.  The row is byte for byte the row
+/// sgpu_encoder_deliver_range wrote for the same packet and flow at the sender,
+/// and valid input for sgpu_frames_parse, sgpu_frames_recv,
+/// sgpu_frames_scan_rows and sgpu_frames_scan_packed.  packetNum_k =
+/// (firstPacketNum + k) mod 2^22, as sgpu_decoder_get_range numbers its packets.
+/// The header is computed on the device from the length read there, so a packet
+/// whose solve is queued in this same submission is framed without a wait.
+///
+/// Everything else is sgpu_decoder_deliver_range's contract: the call never
+/// waits; rows and lengths are in place when the carrying submission
+/// completes; absent packets get results[k] = Siamese_NeedMoreData,
+/// deviceLens[k] = 0 and an untouched row; the call returns Siamese_Success
+/// with *queuedOut = the number of present packets; the lifetime and overlap
+/// rules are the same, and the launch runs after every other launch of its
+/// submission.  A present packet that does not fit, which only the device can
+/// see while its length is pending -- an unreadable or zero prefix, symbol
+/// header plus length past the symbol's capacity, h + n > stride (or a frame
+/// length 7 + n above 2^29 - 1, which no frame can state) -- gets a zeroed row
+/// and deviceLens[k] = 0.  The limit is h + n, not n: a packet that fits
+/// sgpu_decoder_deliver_range's row of the same stride may not fit here.
+///
+/// Siamese_InvalidInput, with nothing queued: sgpu_decoder_deliver_range's
+/// pointer, alignment, stride, packet number and pending-matrix-job rules;
+/// flow > 2^24 - 1 (SGPU_FRAME_NONE included: the bare form is
+/// sgpu_decoder_deliver_range); a packet of the range whose exact length is
+/// already known and does not fit as above.  A dead decoder returns
+/// Siamese_Disabled.  count == 0 returns Siamese_Success with *queuedOut = 0.
+/// A form that packs several frames into one row is not offered.
+SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_frames(SgpuDecoder decoder, unsigned flow, unsigned firstPacketNum,
+                                                         unsigned count, void* deviceDst, size_t stride,
+                                                         unsigned* deviceLens,
+                                                         SiameseResult* results /* host, optional */,
+                                                         unsigned* queuedOut);
 /// sgpu_decode without waiting (see "Deferred outputs" above): the recovered
 /// packets are written to out[0, *countOut), PacketNum at once, Data and
 /// DataBytes at once or when the solve's submission completes.  capacity must
@@ -640,7 +679,7 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range), [7] k_scan
 /// (sgpu_frames_scan_rows: launched on the gather stream, counted once its
 /// gather has been waited for), [8] k_walk (sgpu_frames_scan_packed,
-/// likewise); count entries at most.
+/// likewise), [9] k_relay (sgpu_decoder_deliver_frames); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -661,8 +700,9 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// frame items queued likewise (sgpu_frames_deliver_recovery,
 /// sgpu_encoder_deliver_range), then [23] the rows scanned
 /// (sgpu_frames_scan_rows, counted when the scan is queued), then [24] the
-/// rows scanned by sgpu_frames_scan_packed, counted likewise; count entries at
-/// most.
+/// rows scanned by sgpu_frames_scan_packed, counted likewise, then [25] the
+/// relay items queued (sgpu_decoder_deliver_frames: counted as [21]); count
+/// entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

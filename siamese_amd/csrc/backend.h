@@ -146,6 +146,13 @@ void be_launch_deliver(const DeliverItem* items, uint32_t count, uint32_t maxStr
 /// one (lenBase, and an untouched row, for an absent packet).  Queued beside
 /// be_launch_deliver.
 void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t maxStride);
+/// A decoder's packets forwarded as originals' wire frames into caller-owned
+/// rows (ops.h RelayItem), the grid and maxStride as be_launch_deliver's: each
+/// row gets the frame header computed from the length read on the device, the
+/// payload and a zero tail, and its length word (zero, and an untouched row,
+/// for an absent packet; zero and a zeroed row for one that does not fit).
+/// Queued beside be_launch_deliver.
+void be_launch_relay(const RelayItem* items, uint32_t count, uint32_t maxStride);
 
 /// Block until all queued work has finished.  Returns false on a device fault.
 bool be_sync();
@@ -211,6 +218,7 @@ enum BeKernel
     kBeFrame,
     kBeScan,
     kBeWalk,
+    kBeRelay,
     kBeKernelKinds
 };
 void be_timing_enable(bool on);

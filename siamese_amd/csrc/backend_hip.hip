@@ -19,6 +19,8 @@
 //   k_ge           a decode's recovery matrix and its elimination (opt-in)
 //   k_deliver      decoded packets into caller-owned rows at a fixed stride,
 //                  lengths beside them (k_ingest backwards, opt-in)
+//   k_relay        a decoder's packets forwarded as originals' wire frames, the
+//                  header computed from the length read on the device
 //   k_frame        a sender's originals and recovery packets as wire frames
 //                  into caller-owned rows (header, packet, zero tail; opt-in)
 //   k_scan         frame rows in device memory into 32-byte host records
@@ -3892,6 +3894,133 @@ __global__ __launch_bounds__(64 * kDeliverWaves) void k_frame(const FrameItem* _
 }
 
 // ---------------------------------------------------------------------------
+// Relay (k_relay, ops.h RelayItem)
+//
+// k_deliver's parse in front of k_frame's copy: one wave per (item, 8 KiB
+// chunk of its row), lane L of each 1 KiB tile writes row bytes [16L, 16L+16)
+// with one 16-byte store.  The wave reads the symbol's first aligned word and
+// parses its length prefix (hs = 1..4 bytes, length n) as k_deliver does; the
+// frame's own prefix is that of L = n + 7 (1 byte below 0x80, 2 below 0x4000,
+// 3 below 0x200000, else 4: write_length_prefix's bit patterns), followed by
+// type 0, three flow bytes and three PacketNum bytes, hf = 8..11 bytes held in
+// three dwords.  All of it is wave-uniform.  The packet fits when n >= 1,
+// hs + n <= cap, L fits a prefix and hf + n <= stride (frames.h relay_fits);
+// otherwise the row is zero and its length 0.  Row byte p is symbol byte
+// p - hf + hs, so the source address that lines up with row byte 0 is
+// src + hs - hf: src is 16-byte aligned and hs - hf lies in [-10, -4], so the
+// byte shift (6..12) is never zero and every lane's 16 bytes straddle two
+// aligned source words, loaded (coalesced) only if they hold a byte of
+// [src + hs, src + hs + n) and recombined with v_alignbyte_b32 under a uniform
+// branch, as in k_frame.  The header is merged into lane 0 of tile 0, bytes at
+// and past hf + n are masked to zero and the zero fill runs to the row's end;
+// positions are 64-bit.  Two tiles' loads are in flight before their stores.
+// No LDS, no atomics.
+
+__global__ __launch_bounds__(64 * kDeliverWaves) void k_relay(const RelayItem* __restrict__ items, uint32_t count)
+{
+    const uint32_t ii = __builtin_amdgcn_readfirstlane(blockIdx.x * kDeliverWaves + (threadIdx.x >> 6));
+    if (ii >= count)
+        return;
+    const uint32_t lane = threadIdx.x & 63;
+    const RelayItem it = items[ii];
+    const uint64_t stride = (uint64_t)it.stride16 << 4;
+    uint32_t hs = 0, hf = 0, n = 0;
+    uint32_t h0 = 0, h1 = 0, h2 = 0;   // the frame header, little-endian dwords
+    if (it.src != 0 && it.cap != 0) {   // (uniform)
+        const uint32_t avail = it.cap < 4 ? it.cap : 4;
+        const uint32_t w = __builtin_amdgcn_readfirstlane(ld16(it.src).x) & byte_mask((int)avail);
+        uint32_t len = 0;
+        const int hh = parse_prefix(w, avail, &len);
+        if (hh >= 1 && len >= 1 && (uint32_t)hh + len <= it.cap && len + 7u <= kFrameMaxLength) {
+            const uint32_t Lf = len + 7u;   // type, flow, PacketNum, payload
+            uint32_t pf, pre;               // the frame's prefix: bytes, and the bytes as a little-endian dword
+            if (Lf < 0x80u) {
+                pf = 1;
+                pre = Lf;
+            } else if (Lf < 0x4000u) {
+                pf = 2;
+                pre = (0x80u | (Lf >> 8)) | ((Lf & 0xffu) << 8);
+            } else if (Lf < 0x200000u) {
+                pf = 3;
+                pre = (0xC0u | (Lf >> 16)) | (((Lf >> 8) & 0xffu) << 8) | ((Lf & 0xffu) << 16);
+            } else {
+                pf = 4;
+                pre = (0xE0u | (Lf >> 24)) | (((Lf >> 16) & 0xffu) << 8) | (((Lf >> 8) & 0xffu) << 16) |
+                      ((Lf & 0xffu) << 24);
+            }
+            if ((uint64_t)pf + Lf <= stride) {
+                hs = (uint32_t)hh;
+                n = len;
+                hf = pf + 7u;
+                // type 0, flow and PacketNum as 56 bits behind the prefix
+                const uint64_t body = ((uint64_t)(it.flow & 0xffffffu) << 8) | ((uint64_t)(it.packetNum & 0xffffffu) << 32);
+                const uint32_t s = 8u * pf;   // 8..32
+                const uint64_t lo = (uint64_t)pre | (body << s);
+                h0 = (uint32_t)lo;
+                h1 = (uint32_t)(lo >> 32);
+                h2 = (uint32_t)(body >> (64u - s));
+            }
+        }
+    }
+    const uint64_t total = (uint64_t)hf + n;   // row bytes in use (0: a zeroed row)
+    if (blockIdx.y == 0 && lane == 0)
+        *reinterpret_cast<GMEM uint32_t*>(it.lenOut) = (uint32_t)total;
+    if (it.src == 0)   // an absent packet: its row stays as it is
+        return;
+    // source address that lines up with row byte 0, and the payload's span
+    const uint64_t src = it.src + hs;
+    const uint64_t base = src - hf;
+    const unsigned sh = (unsigned)(base & 15u);   // 6..12 (0 for a zeroed row: nothing is loaded)
+    const unsigned q = sh >> 2, r = sh & 3;
+    const uint64_t srcEnd = src + n;
+    const uint64_t step = (uint64_t)gridDim.y * kIngestChunkBytes;
+    for (uint64_t c0 = (uint64_t)blockIdx.y * kIngestChunkBytes; c0 < stride; c0 += step) {
+        const uint64_t c1 = c0 + kIngestChunkBytes < stride ? c0 + kIngestChunkBytes : stride;
+        for (uint64_t t = c0; t < c1; t += 2 * kTileBytes) {
+            uint4 out[2];
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                out[u] = make_uint4(0, 0, 0, 0);
+                if (p >= total)   // the zero fill: nothing to load
+                    continue;
+                const uint64_t a = (base + p) & ~(uint64_t)15;
+                const uint4 lo = (a < srcEnd && a + 16 > src) ? ld16(a) : make_uint4(0, 0, 0, 0);
+                const uint4 hi = a + 16 < srcEnd ? ld16(a + 16) : make_uint4(0, 0, 0, 0);
+                const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                switch (q) {   // wave-uniform; 1..3 for a row in use
+                case 1:
+                    out[u] = make_uint4(pick(w, 1, r, 0), pick(w, 1, r, 1), pick(w, 1, r, 2), pick(w, 1, r, 3));
+                    break;
+                case 2:
+                    out[u] = make_uint4(pick(w, 2, r, 0), pick(w, 2, r, 1), pick(w, 2, r, 2), pick(w, 2, r, 3));
+                    break;
+                default:
+                    out[u] = make_uint4(pick(w, 3, r, 0), pick(w, 3, r, 1), pick(w, 3, r, 2), pick(w, 3, r, 3));
+                    break;
+                }
+            }
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                if (p >= stride)
+                    continue;
+                uint4 v = out[u];
+                if (p == 0) {   // the frame header (8..11 bytes; none for a zeroed row) over source bytes
+                    const uint32_t m0 = byte_mask((int)hf), m1 = byte_mask((int)hf - 4), m2 = byte_mask((int)hf - 8);
+                    v.x = (v.x & ~m0) | (h0 & m0);
+                    v.y = (v.y & ~m1) | (h1 & m1);
+                    v.z = (v.z & ~m2) | (h2 & m2);
+                }
+                if (p + 16 > total)
+                    v = mask16(v, p < total ? (int)(total - p) : 0);
+                st16(it.dst + p, v);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Row scan (k_scan, ops.h RowHead)
 //
 // The way in for frame rows that exist only in device memory: one lane per
@@ -4590,6 +4719,18 @@ void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t maxStride)
     const uint32_t chunks =
         std::min(kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxStride + kIngestChunkBytes - 1) / kIngestChunkBytes)));
     hipLaunchKernelGGL(k_frame, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
+                       g_stream, items, count);
+}
+
+void be_launch_relay(const RelayItem* items, uint32_t count, uint32_t maxStride)
+{
+    if (count == 0)
+        return;
+    Timed t(kBeRelay);
+    // (the grid of be_launch_deliver)
+    const uint32_t chunks =
+        std::min(kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxStride + kIngestChunkBytes - 1) / kIngestChunkBytes)));
+    hipLaunchKernelGGL(k_relay, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
                        g_stream, items, count);
 }
 

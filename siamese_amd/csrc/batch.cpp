@@ -409,6 +409,26 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_range(SgpuDecoder decoder, uns
     return r;
 }
 
+SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_frames(SgpuDecoder decoder, unsigned flow, unsigned firstPacketNum,
+                                                         unsigned count, void* deviceDst, size_t stride,
+                                                         unsigned* deviceLens, SiameseResult* results,
+                                                         unsigned* queuedOut)
+{
+    if (queuedOut)
+        *queuedOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, lens = (uint64_t)(uintptr_t)deviceLens;
+    // (SGPU_FRAME_NONE is above kFrameMaxFlow: the bare form is sgpu_decoder_deliver_range)
+    if (!decoder || BD(decoder)->core.ge_pending() || !frame_rows_ok(count, dst, stride, lens) ||
+        flow > kFrameMaxFlow || firstPacketNum > SIAMESE_PACKET_NUM_MAX)
+        return Siamese_InvalidInput;
+    unsigned queued = 0;
+    const SiameseResult r = BD(decoder)->core.deliver_frames(firstPacketNum, count, flow, dst, (uint64_t)stride,
+                                                             lens, results, &queued);
+    if (queuedOut)
+        *queuedOut = queued;
+    return r;
+}
+
 SIAMESE_EXPORT SiameseResult sgpu_decode_deferred(SgpuDecoder decoder, SiameseOriginalPacket* out,
                                                   unsigned capacity, unsigned* countOut)
 {
@@ -869,13 +889,14 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[25] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[26] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
                             s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide,
-                            s.delivers,   s.frames,      s.scans,      Engine::global()->walks()};
-    for (unsigned k = 0; k < count && k < 25; ++k)
+                            s.delivers,   s.frames,      s.scans,      Engine::global()->walks(),
+                            s.relays};
+    for (unsigned k = 0; k < count && k < 26; ++k)
         out[k] = v[k];
 }
 

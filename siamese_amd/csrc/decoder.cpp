@@ -1,6 +1,7 @@
 // decoder.cpp -- see decoder.h.  Line citations are to the reference
 // SiameseDecoder.cpp unless stated otherwise.
 #include "decoder.h"
+#include "frames.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2759,6 +2760,37 @@ SiameseResult DecoderCore::deliver_range(unsigned firstNum, unsigned count, uint
         // the recovered prefix and checks it against them and the stride)
         prog_.deliver(present ? s->buf.addr() : 0, present ? s->bytes : 0, dst + (uint64_t)k * stride,
                       lens + (uint64_t)k * 4, stride);
+        if (results)
+            results[k] = present ? Siamese_Success : Siamese_NeedMoreData;
+        if (present)
+            ++*queued;
+    }
+    return Siamese_Success;
+}
+
+SiameseResult DecoderCore::deliver_frames(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst,
+                                          uint64_t stride, uint64_t lens, SiameseResult* results, unsigned* queued)
+{
+    *queued = 0;
+    settle();
+    if (dead())
+        return Siamese_Disabled;
+    // deliver_range's two passes; a known length is judged as the device
+    // judges a pending one (frames.h relay_fits: the limit is header + length)
+    const unsigned e0 = column_to_element(firstNum);
+    unsigned e = e0;
+    for (unsigned k = 0; k < count; ++k, e = (e + 1) % kColumnPeriod)
+        if (e < count_) {
+            const DecSlot& s = slot(e);
+            if (s.bytes != 0 && !s.pending && !relay_fits(s.header, s.bytes - s.header, s.bytes, stride))
+                return Siamese_InvalidInput;
+        }
+    e = e0;
+    for (unsigned k = 0; k < count; ++k, e = (e + 1) % kColumnPeriod) {
+        const DecSlot* s = e < count_ ? &slot(e) : nullptr;
+        const bool present = s && s->bytes != 0;
+        prog_.relay(present ? s->buf.addr() : 0, present ? s->bytes : 0, flow, (firstNum + k) & SIAMESE_PACKET_NUM_MAX,
+                    dst + (uint64_t)k * stride, lens + (uint64_t)k * 4, stride);
         if (results)
             results[k] = present ? Siamese_Success : Siamese_NeedMoreData;
         if (present)

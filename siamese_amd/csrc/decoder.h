@@ -140,6 +140,14 @@ public:
     /// queued, when a packet's known length exceeds the stride.
     SiameseResult deliver_range(unsigned firstNum, unsigned count, uint64_t dst, uint64_t stride, uint64_t lens,
                                 SiameseResult* results, unsigned* queued);
+    /// sgpu_decoder_deliver_frames: deliver_range with each present packet
+    /// written as the wire frame of an original of `flow` (Program::relay: the
+    /// device computes the frame header from the length it reads, frames.h
+    /// relay_row), the frame's PacketNum (firstNum + k) mod 2^22 as get_range
+    /// numbers its packets.  InvalidInput, with nothing queued, when a packet's
+    /// known length plus its frame header exceeds the stride.
+    SiameseResult deliver_frames(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst, uint64_t stride,
+                                 uint64_t lens, SiameseResult* results, unsigned* queued);
     /// Host-memory recovery packet (drop-in API).
     SiameseResult add_recovery(const SiameseRecoveryPacket& packet);
     /// Device-resident recovery packet (batch API).

@@ -54,6 +54,7 @@ void EngineStats::add(const EngineStats& o)
     delivers += o.delivers;
     frames += o.frames;
     scans += o.scans;
+    relays += o.relays;
 }
 
 namespace {
@@ -118,6 +119,7 @@ void ProgramBody::clear()
     lcb.clear();
     ndeliver = 0;   // (the items' vector keeps its elements: not touched here)
     nframe = 0;
+    nrelay = 0;
     gateOpen = false;
 }
 
@@ -907,6 +909,23 @@ void Program::frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t h
     b_->frames[b_->nframe++] = it;
 }
 
+void Program::relay(uint64_t src, uint32_t cap, uint32_t flow, uint32_t packetNum, uint64_t dst, uint64_t lenOut,
+                    uint64_t stride)
+{
+    touch();
+    RelayItem it;
+    it.src = src;
+    it.dst = dst;
+    it.lenOut = lenOut;
+    it.cap = cap;
+    it.stride16 = (uint32_t)(stride >> 4);
+    it.flow = flow;
+    it.packetNum = packetNum;
+    if (b_->nrelay == b_->relays.size())
+        b_->relays.emplace_back();
+    b_->relays[b_->nrelay++] = it;
+}
+
 // ---------------------------------------------------------------------------
 // Shard queues
 
@@ -1455,6 +1474,8 @@ struct Batch
     uint32_t maxDeliverStride = 0;         // ... their longest row in bytes, saturated (k_deliver's grid)
     size_t oFrame = 0, nFrame = 0;         // frame items of every body (ops.h FrameItem)
     uint32_t maxFrameStride = 0;           // ... their longest row, as maxDeliverStride (k_frame's grid)
+    size_t oRelay = 0, nRelay = 0;         // relay items of every body (ops.h RelayItem)
+    uint32_t maxRelayStride = 0;           // ... their longest row, as maxDeliverStride (k_relay's grid)
     size_t oCopy = 0;                      // the download copy list (BeCopy records)
     uint64_t wideBase = 0;                 // this submission's k_ldpc scratch: bytes into the ring
     bool wideGated = false;                // k_ldpc items of gated ops: the launches take the gate
@@ -2198,11 +2219,13 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     size_t geInBytes = 0;
     size_t nDeliver = 0;   // delivery items of every body
     size_t nFrame = 0;     // frame items of every body
+    size_t nRelay = 0;     // relay items of every body
     for (int g = 0; g < 2; ++g)
         for (size_t pi = 0; pi < bt.bodies[g].size(); ++pi) {
             const ProgramBody* p = bt.bodies[g][pi];
             nDeliver += p->ndeliver;   // (beside nges: no line of the body this pass does not read anyway)
             nFrame += p->nframe;
+            nRelay += p->nrelay;
             for (size_t k = 0; k < p->nges; ++k) {
                 const ProgramBody::PendingGe& ge = p->ges[k];
                 GeDesc d;
@@ -2238,6 +2261,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     bt.nGe = gdescs.size();
     bt.nDeliver = nDeliver;
     bt.nFrame = nFrame;
+    bt.nRelay = nRelay;
 
     constexpr size_t kIngestChunk = SGPU_INGEST_CHUNK;
     size_t nIngest = 0, stageBytes = 0, nIngBlocks = 0;
@@ -2305,6 +2329,9 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     // the frame items, likewise (one k_frame launch beside k_deliver's)
     bt.oFrame = off;
     off = align16(off + nFrame * sizeof(FrameItem));
+    // the relay items, likewise (one k_relay launch beside them)
+    bt.oRelay = off;
+    off = align16(off + nRelay * sizeof(RelayItem));
     // the download copy list (the counters and results, then every range)
     size_t nDownloads = 0;
     for (const Shard::Queues& q : bt.queues)
@@ -2527,6 +2554,20 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
             }
         bt.maxFrameStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
     }
+    if (nRelay) {
+        RelayItem* ri = (RelayItem*)(up + bt.oRelay);
+        uint32_t max16 = 0;
+        for (int g = 0; g < 2; ++g)
+            for (const ProgramBody* p : bt.bodies[g]) {
+                if (p->nrelay == 0)
+                    continue;
+                std::memcpy(ri, p->relays.data(), p->nrelay * sizeof(RelayItem));
+                for (uint32_t k = 0; k < p->nrelay; ++k)
+                    max16 = std::max(max16, ri[k].stride16);
+                ri += p->nrelay;
+            }
+        bt.maxRelayStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
+    }
 
     // download area: the byte counters (kAcctBytes), the solve results, then
     // each requested range
@@ -2558,9 +2599,10 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
 
     st.flushes = 1;
     st.launches = phases.size() + (nIngest ? 1 : 0) + (gdescs.empty() ? 0 : 1) + (nDeliver ? 1 : 0) +
-                  (nFrame ? 1 : 0);
+                  (nFrame ? 1 : 0) + (nRelay ? 1 : 0);
     st.delivers = nDeliver;
     st.frames = nFrame;
+    st.relays = nRelay;
     st.ops = nOps;
     st.terms = nTerms;
     st.solves = sdescs.size();
@@ -2684,6 +2726,10 @@ void Engine::launch_batch(Batch& bt)
     // this submission released is still untouched
     if (bt.nFrame)
         be_launch_frame((const FrameItem*)(bt.upBase + bt.oFrame), (uint32_t)bt.nFrame, bt.maxFrameStride);
+    // ... and its relay items, on k_deliver's terms: a packet recovered in this
+    // submission is forwarded from its final bytes, its length prefix included
+    if (bt.nRelay)
+        be_launch_relay((const RelayItem*)(bt.upBase + bt.oRelay), (uint32_t)bt.nRelay, bt.maxRelayStride);
     // the counters and solve results, then the downloads, in one call (one
     // kernel when small; its range list was laid out with the upload: a
     // drop-in submission carries a range per application call)

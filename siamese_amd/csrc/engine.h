@@ -311,6 +311,7 @@ struct ProgramBody
     // a body without deliveries costs detach and assembly no cache line more
     uint32_t ndeliver = 0;
     uint32_t nframe = 0;   // items in `frames` (below), kept here for the same reason
+    uint32_t nrelay = 0;   // items in `relays` (below), likewise
     std::vector<Completion> callbacks;
     // objects the callbacks use, kept alive until they have run (so a
     // callback captures a raw pointer and fits std::function's inline
@@ -353,6 +354,10 @@ struct ProgramBody
     /// FrameItem), run by the submission's one k_frame launch beside
     /// k_deliver's.  nframe in use (capacity is kept).
     std::vector<FrameItem> frames;
+    /// A decoder's packets to forward as wire frames into the caller's device
+    /// rows (ops.h RelayItem), run by the submission's one k_relay launch
+    /// beside k_deliver's.  nrelay in use (capacity is kept).
+    std::vector<RelayItem> relays;
     void lc_seal();                     // seals the open OP_LINCOMBS batch
     /// Move the segment's last op (an OP_LINCOMB) into the open batch, or
     /// seal the batch first when they are not independent.
@@ -362,7 +367,7 @@ struct ProgramBody
 
     bool empty() const
     {
-        return nges == 0 && ndeliver == 0 && nframe == 0 &&
+        return nges == 0 && ndeliver == 0 && nframe == 0 && nrelay == 0 &&
                (nsegs == 0 ||
                 (nsegs == 1 && segs[0].ops.empty() && copies.empty() && lcb.items.empty() && !rb.open));
     }
@@ -534,6 +539,15 @@ public:
     void frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t hdrLen, uint64_t dst, uint64_t lenOut,
                uint64_t stride, uint32_t lenBase = 0);
 
+    /// Queue a relay item (ops.h RelayItem): deliver()'s arguments, and the
+    /// flow and PacketNum of the original's frame the device writes in front of
+    /// the payload once it has read the symbol's length.  Ordered as
+    /// deliver()'s items: one launch after the submission's last executor /
+    /// solve launch.  A program whose only work is relay items still makes a
+    /// submission.
+    void relay(uint64_t src, uint32_t cap, uint32_t flow, uint32_t packetNum, uint64_t dst, uint64_t lenOut,
+               uint64_t stride);
+
     bool empty() const { return !b_ || b_->empty(); }
 
 private:
@@ -579,6 +593,7 @@ struct EngineStats
     uint64_t delivers = 0;        // delivery items queued (sgpu_decoder_deliver_range)
     uint64_t frames = 0;          // frame items queued (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range)
     uint64_t scans = 0;           // rows scanned (sgpu_frames_scan_rows), counted when the scan is queued
+    uint64_t relays = 0;          // relay items queued (sgpu_decoder_deliver_frames)
 
     void add(const EngineStats& o);
 };

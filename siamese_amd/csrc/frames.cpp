@@ -7,34 +7,7 @@ namespace sgpu {
 namespace {
 constexpr unsigned kOriginalHeader = kFrameOriginalInner;
 constexpr unsigned kRecoveryHeader = kFrameRecoveryInner;
-
-inline unsigned prefix_bytes(unsigned length)
-{
-    return length < 0x80 ? 1 : length < 0x4000 ? 2 : length < 0x200000 ? 3 : 4;
-}
 } // namespace
-
-unsigned frame_header_bytes(unsigned type, unsigned dataBytes)
-{
-    const unsigned inner = (type == kFrameOriginal ? kOriginalHeader : kRecoveryHeader);
-    return prefix_bytes(inner + dataBytes) + inner;
-}
-
-unsigned frame_write_header(unsigned type, unsigned flow, unsigned packetNum, unsigned dataBytes, uint8_t* out)
-{
-    const unsigned inner = (type == kFrameOriginal ? kOriginalHeader : kRecoveryHeader);
-    unsigned n = write_length_prefix(inner + dataBytes, out);
-    out[n++] = (uint8_t)type;
-    out[n++] = (uint8_t)flow;
-    out[n++] = (uint8_t)(flow >> 8);
-    out[n++] = (uint8_t)(flow >> 16);
-    if (type == kFrameOriginal) {
-        out[n++] = (uint8_t)packetNum;
-        out[n++] = (uint8_t)(packetNum >> 8);
-        out[n++] = (uint8_t)(packetNum >> 16);
-    }
-    return n;
-}
 
 long frames_parse(const uint8_t* buf, size_t bytes, FrameInfo* out, size_t maxFrames, size_t* consumed,
                   size_t* badOffset)

@@ -44,9 +44,30 @@ struct FrameInfo
 };
 
 /// Header bytes before the data of a frame of `type` holding `dataBytes`.
-unsigned frame_header_bytes(unsigned type, unsigned dataBytes);
+/// (This and frame_write_header are defined here: relay_row is built from
+/// them, and the test double is also built without frames.cpp.)
+inline unsigned frame_header_bytes(unsigned type, unsigned dataBytes)
+{
+    const unsigned inner = type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+    const unsigned length = inner + dataBytes;
+    return (length < 0x80 ? 1 : length < 0x4000 ? 2 : length < 0x200000 ? 3 : 4) + inner;
+}
 /// Writes the header; returns its size (frame_header_bytes).
-unsigned frame_write_header(unsigned type, unsigned flow, unsigned packetNum, unsigned dataBytes, uint8_t* out);
+inline unsigned frame_write_header(unsigned type, unsigned flow, unsigned packetNum, unsigned dataBytes, uint8_t* out)
+{
+    const unsigned inner = type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+    unsigned n = write_length_prefix(inner + dataBytes, out);
+    out[n++] = (uint8_t)type;
+    out[n++] = (uint8_t)flow;
+    out[n++] = (uint8_t)(flow >> 8);
+    out[n++] = (uint8_t)(flow >> 16);
+    if (type == kFrameOriginal) {
+        out[n++] = (uint8_t)packetNum;
+        out[n++] = (uint8_t)(packetNum >> 8);
+        out[n++] = (uint8_t)(packetNum >> 16);
+    }
+    return n;
+}
 /// No malformed frame was met (frames_parse's *badOffset).
 constexpr size_t kNoBadFrame = ~(size_t)0;
 /// Parses frames from buf[0, bytes) (bytes < 4 GiB: offsets are 32-bit).
@@ -204,6 +225,39 @@ inline uint32_t row_walk(const uint8_t* row, uint64_t stride, const uint32_t* le
         at += (uint64_t)h + length;
     }
     return n;
+}
+
+/// What k_relay computes for one present item (ops.h RelayItem): the symbol
+/// sym, of which cap bytes may be read, as the wire frame of original
+/// packetNum of `flow` in row[0, stride), its length in *len.  With hs and n
+/// the symbol's prefix bytes and length and hf = frame_header_bytes(
+/// kFrameOriginal, n), the packet fits when the prefix can be read from
+/// min(cap, 4) bytes, n >= 1, hs + n <= cap, hf + n <= stride and the frame's
+/// own L = 7 + n fits a length prefix (kFrameMaxLength); then row[0, hf) is
+/// frame_write_header's header, row[hf, hf + n) = sym[hs, hs + n), the rest of
+/// the row is zero and *len = hf + n.  A packet that does not fit gets a zero
+/// row and *len = 0.  Reads only sym[0, min(cap, hs + n)), writes only
+/// row[0, stride) and *len.
+inline bool relay_fits(unsigned hs, unsigned n, uint32_t cap, uint64_t stride)
+{
+    return n >= 1 && (uint64_t)hs + n <= cap && (uint64_t)n + kFrameOriginalInner <= kFrameMaxLength &&
+           (uint64_t)frame_header_bytes(kFrameOriginal, n) + n <= stride;
+}
+inline void relay_row(const uint8_t* sym, uint32_t cap, uint32_t flow, uint32_t packetNum, uint8_t* row,
+                      uint64_t stride, uint32_t* len)
+{
+    uint8_t hdr[kFrameMaxHeader];
+    unsigned hs = 0, hf = 0, n = 0, length = 0;
+    const int h = read_length_prefix(sym, cap < 4 ? cap : 4u, &length);
+    if (h >= 1 && relay_fits((unsigned)h, length, cap, stride)) {
+        hs = (unsigned)h;
+        n = length;
+        hf = frame_write_header(kFrameOriginal, flow, packetNum, n, hdr);
+    }
+    std::memcpy(row, hdr, hf);
+    std::memcpy(row + hf, sym + hs, n);
+    std::memset(row + hf + n, 0, (size_t)(stride - hf - n));
+    *len = hf + n;
 }
 
 } // namespace sgpu

@@ -430,6 +430,7 @@ constexpr uint32_t kDeliverMaxChunks = 4096;
 /// original's is prefix <= 4 plus 7 bytes), hdrLen = 0 for a bare packet.  The
 /// launch runs after every other launch of its submission, beside k_deliver.
 constexpr unsigned kFrameMaxHeader = 11;
+constexpr unsigned kFrameMaxLength = 0x1fffffff;   // the largest L a frame's 4-byte length prefix holds
 struct FrameItem
 {
     uint64_t src;        // the packet's first byte (0: absent)
@@ -444,6 +445,33 @@ struct FrameItem
 static_assert(sizeof(FrameItem) == 48, "FrameItem layout");
 /// k_frame's grid is k_deliver's: kDeliverWaves items per workgroup, at most
 /// kDeliverMaxChunks chunk rows.
+
+/// One decoder packet forwarded as an original's wire frame into a
+/// caller-owned device row (k_relay, sgpu_decoder_deliver_frames): DeliverItem
+/// with the frame header computed on the device from the length it reads.  The
+/// symbol at src (16-byte aligned, its 1-4 byte length prefix at byte 0) gives
+/// its header hs and length n as for k_deliver; the frame header of an original
+/// of n bytes for `flow` and `packetNum` (frames.h frame_write_header) has hf =
+/// 8..11 bytes.  Valid when n >= 1, hs + n <= cap and hf + n <= stride: then
+/// dst[0, hf) = that header, dst[hf, hf + n) = src[hs, hs + n),
+/// dst[hf + n, stride) = 0 and *lenOut = hf + n; an invalid packet gets a zeroed
+/// row and *lenOut = 0.  src = 0: an absent packet, only *lenOut = 0 is written.
+/// Only aligned 16-byte words holding a byte of [src, src + cap) are read,
+/// nothing outside [dst, dst + stride) and the length word is written
+/// (frames.h relay_row states the row in plain C++).  The launch runs after
+/// every other launch of its submission, beside k_deliver and k_frame.
+struct RelayItem
+{
+    uint64_t src;        // the symbol (0: absent)
+    uint64_t dst;        // the row, 16-byte aligned
+    uint64_t lenOut;     // uint32 length word, 4-byte aligned
+    uint32_t cap;        // as DeliverItem.cap
+    uint32_t stride16;   // the row's bytes / 16 (1 .. 2^28)
+    uint32_t flow;       // the frame's flow (<= 2^24 - 1)
+    uint32_t packetNum;  // the frame's PacketNum
+};
+static_assert(sizeof(RelayItem) == 40, "RelayItem layout");
+/// k_relay's grid is k_deliver's too.
 
 /// What the host needs of one frame row that lives in device memory (k_scan,
 /// sgpu_frames_scan_rows): the layout of SgpuRowHead (include/siamese_gpu.h),

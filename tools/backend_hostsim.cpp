@@ -497,6 +497,21 @@ void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t)
     }
 }
 
+// k_relay (ops.h RelayItem): frames.h relay_row for every present item; an
+// absent packet only its zero length word.
+void be_launch_relay(const RelayItem* items, uint32_t count, uint32_t)
+{
+    if (noexec())
+        return;
+    for (uint32_t i = 0; i < count; ++i) {
+        const RelayItem& it = items[i];
+        uint32_t lw = 0;
+        if (it.src != 0)
+            relay_row(P(it.src), it.cap, it.flow, it.packetNum, P(it.dst), (uint64_t)it.stride16 << 4, &lw);
+        std::memcpy(P(it.lenOut), &lw, 4);
+    }
+}
+
 static void solve_prefix(const SolveDesc* solves, const SolveRow* rows, const uint8_t* coef,
                             uint32_t* results, uint32_t count, uint64_t* acct)
 {
