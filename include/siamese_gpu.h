@@ -234,7 +234,7 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_range(SgpuDecoder decoder, uns
 /// sgpu_decoder_deliver_range); a packet of the range whose exact length is
 /// already known and does not fit as above.  A dead decoder returns
 /// Siamese_Disabled.  count == 0 returns Siamese_Success with *queuedOut = 0.
-/// A form that packs several frames into one row is not offered.
+/// The form that packs several frames into one row is sgpu_decoder_pack_frames.
 SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_frames(SgpuDecoder decoder, unsigned flow, unsigned firstPacketNum,
                                                          unsigned count, void* deviceDst, size_t stride,
                                                          unsigned* deviceLens,
@@ -668,6 +668,51 @@ SIAMESE_EXPORT SiameseResult sgpu_encoder_pack_frames(SgpuEncoder encoder, unsig
                                                       unsigned maxRows, unsigned* deviceLens,
                                                       SiameseResult* results /* host, originalCount, optional */,
                                                       unsigned* rowsOut, unsigned* framesOut);
+/// sgpu_encoder_pack_frames at a relay: the present packets firstPacketNum ..
+/// firstPacketNum+count-1 of `decoder`, ascending, each as the
+/// SGPU_FRAME_ORIGINAL frame sgpu_decoder_deliver_frames writes for it (header
+/// from sgpu_frame_write_header for `flow` and (firstPacketNum + k) mod 2^22,
+/// then the payload), laid out by the rule above.  The layout is made on the
+/// device, from the lengths it reads there, so a packet whose solve is queued
+/// in this same submission (sgpu_decode, sgpu_decode_device) is packed without
+/// a wait and the host learns the row count only from deviceInfo.
+///
+/// An absent packet takes no space and gets results[k] = Siamese_NeedMoreData.
+/// A present packet that does not fit, as sgpu_decoder_deliver_frames defines
+/// it for a row of `stride` bytes (an unreadable or zero prefix, a length past
+/// the symbol's capacity, T > stride, a frame length above 2^29 - 1), which
+/// only the device can see while its length is pending, takes no space either.
+///
+/// With rows = the rows the layout needs: rows [0, min(rows, maxRows)) are
+/// written whole (zero between the frames and to each row's end) and
+/// deviceLens[r] = the end of row r's last frame; deviceLens[r] = 0 for the
+/// other r < maxRows and those rows are left untouched.  deviceInfo[0] = rows
+/// (it may exceed maxRows), [1] = the frames written, [2] = the present packets
+/// skipped as not fitting, [3] = the frames not written because their row was
+/// >= maxRows; nothing at or past row maxRows is touched.  The written rows are
+/// a valid frame stream for sgpu_frames_parse / sgpu_frames_recv and valid
+/// input for sgpu_frames_scan_packed; when the decoder holds exactly the
+/// packets the sender holds they are, with the lengths, byte for byte what
+/// sgpu_encoder_pack_frames(encoder, flow, firstPacketNum, count, NULL, 0, ...)
+/// wrote there.  Never waits; everything is in place when the carrying
+/// submission completes; the lifetime and overlap rules are
+/// sgpu_decoder_deliver_frames', deviceInfo included.
+///
+/// Returns Siamese_Success with *queuedOut = the number of present packets.
+/// Siamese_InvalidInput, with nothing queued: sgpu_decoder_deliver_frames'
+/// pointer, alignment, stride, packet number and pending-matrix-job rules
+/// (deviceDst and deviceLens may be null only when maxRows is 0); deviceInfo
+/// null or not 16-byte aligned; flow > 2^24 - 1 (SGPU_FRAME_NONE included);
+/// count > 65535; a packet whose length is already known and does not fit.  A
+/// dead decoder returns Siamese_Disabled.  count == 0 returns Siamese_Success,
+/// writes no row, zeroes the maxRows length words and writes a zero deviceInfo.
+/// Recovery frames are not carried (a relay re-encodes: INTEGRATION).
+SIAMESE_EXPORT SiameseResult sgpu_decoder_pack_frames(SgpuDecoder decoder, unsigned flow, unsigned firstPacketNum,
+                                                      unsigned count, void* deviceDst, size_t stride, unsigned maxRows,
+                                                      unsigned* deviceLens,
+                                                      unsigned* deviceInfo /* 4 x uint32, device, 16-byte aligned */,
+                                                      SiameseResult* results /* host, count, optional */,
+                                                      unsigned* queuedOut);
 
 /// Device timing of flushed work since the last reset (milliseconds).
 SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* totalMs);
@@ -679,7 +724,8 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range), [7] k_scan
 /// (sgpu_frames_scan_rows: launched on the gather stream, counted once its
 /// gather has been waited for), [8] k_walk (sgpu_frames_scan_packed,
-/// likewise), [9] k_relay (sgpu_decoder_deliver_frames); count entries at most.
+/// likewise), [9] k_relay (sgpu_decoder_deliver_frames), [10] k_plan and [11]
+/// k_pack (sgpu_decoder_pack_frames); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -701,8 +747,9 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// sgpu_encoder_deliver_range), then [23] the rows scanned
 /// (sgpu_frames_scan_rows, counted when the scan is queued), then [24] the
 /// rows scanned by sgpu_frames_scan_packed, counted likewise, then [25] the
-/// relay items queued (sgpu_decoder_deliver_frames: counted as [21]); count
-/// entries at most.
+/// relay items queued (sgpu_decoder_deliver_frames: counted as [21]), then
+/// [26] the pack items queued (sgpu_decoder_pack_frames: one per packet of the
+/// range, absent ones included); count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

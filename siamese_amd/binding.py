@@ -71,6 +71,15 @@ def bind_packed_abi(L):
     return L
 
 
+def bind_relay_pack_abi(L):
+    """Prototype of sgpu_decoder_pack_frames: a decoder's packets as wire
+    frames packed several to a row, laid out on the device."""
+    vp, u, sz = ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t
+    L.sgpu_decoder_pack_frames.restype = ctypes.c_int
+    L.sgpu_decoder_pack_frames.argtypes = [vp, u, u, u, vp, sz, u, vp, vp, vp, vp]
+    return L
+
+
 class SiameseError(RuntimeError):
     def __init__(self, what, code):
         name = RESULT_NAMES[code] if 0 <= code < 6 else str(code)

@@ -153,6 +153,15 @@ void be_launch_frame(const FrameItem* items, uint32_t count, uint32_t maxStride)
 /// for an absent packet; zero and a zeroed row for one that does not fit).
 /// Queued beside be_launch_deliver.
 void be_launch_relay(const RelayItem* items, uint32_t count, uint32_t maxStride);
+/// A decoder's packets forwarded as wire frames, several to a row (ops.h
+/// PackJob, PackItem, PlanRec): k_plan lays out every job's frames from the
+/// lengths it reads on the device, into plan[0, count), and writes the jobs'
+/// length words and info records; k_pack then writes every planned frame and
+/// the zeros of its span.  plan is device memory of the submission, count
+/// records, which the host never reads; maxStride is the longest row in bytes,
+/// saturated at 2^32 - 1 (k_pack's grid).  Queued beside be_launch_deliver.
+void be_launch_pack(const PackJob* jobs, uint32_t jobCount, const PackItem* items, uint32_t count, PlanRec* plan,
+                    uint32_t maxStride);
 
 /// Block until all queued work has finished.  Returns false on a device fault.
 bool be_sync();
@@ -219,6 +228,8 @@ enum BeKernel
     kBeScan,
     kBeWalk,
     kBeRelay,
+    kBePlan,
+    kBePack,
     kBeKernelKinds
 };
 void be_timing_enable(bool on);

@@ -21,6 +21,8 @@
 //                  lengths beside them (k_ingest backwards, opt-in)
 //   k_relay        a decoder's packets forwarded as originals' wire frames, the
 //                  header computed from the length read on the device
+//   k_plan, k_pack the same frames several to a row: the packer's layout made
+//                  on the device from those lengths, then k_relay's copy
 //   k_frame        a sender's originals and recovery packets as wire frames
 //                  into caller-owned rows (header, packet, zero tail; opt-in)
 //   k_scan         frame rows in device memory into 32-byte host records
@@ -4021,6 +4023,231 @@ __global__ __launch_bounds__(64 * kDeliverWaves) void k_relay(const RelayItem* _
 }
 
 // ---------------------------------------------------------------------------
+// Relay into packed rows (k_plan and k_pack; ops.h PackJob, PackItem, PlanRec)
+//
+// k_relay with several frames to a row.  Where a frame goes depends on the
+// length of every frame before it, and the length of a packet recovered in
+// this submission exists only here, so the layout is made on the device:
+// k_plan runs the packer's cursor rule (frames.h pack_plan) over the lengths
+// and leaves one 16-byte record per item, k_pack is k_relay's copy with the
+// destination, the span to fill and the item's validity taken from its record.
+
+// k_relay's test on one symbol (frames.h relay_fits): w = the symbol's first
+// dword, cap its readable bytes, limit the bytes the frame may take.  Returns
+// the frame's own prefix bytes (1..4: the frame is pf + 7 + *n bytes), or 0
+// with *hs = *n = 0 for a packet that does not fit.
+__device__ __forceinline__ uint32_t relay_sizes(uint32_t w, uint32_t cap, uint64_t limit, uint32_t* hs, uint32_t* n)
+{
+    *hs = 0;
+    *n = 0;
+    if (cap == 0)
+        return 0;
+    const uint32_t avail = cap < 4 ? cap : 4;
+    uint32_t len = 0;
+    const int hh = parse_prefix(w & byte_mask((int)avail), avail, &len);
+    if (hh < 1 || len < 1 || (uint32_t)hh + len > cap || len + 7u > kFrameMaxLength)
+        return 0;
+    const uint32_t Lf = len + 7u;   // type, flow, PacketNum, payload
+    const uint32_t pf = Lf < 0x80u ? 1u : Lf < 0x4000u ? 2u : Lf < 0x200000u ? 3u : 4u;
+    if ((uint64_t)pf + Lf > limit)
+        return 0;
+    *hs = (uint32_t)hh;
+    *n = len;
+    return pf;
+}
+
+// k_plan: one wave per job.  64 items at a time, lane L reads item b + L's
+// first symbol dword (a 4-byte load at the 16-byte aligned symbol) and computes
+// its frame's bytes T, 0 for an absent packet or one that does not fit; such
+// an item's record is zero and is stored by its own lane.  The wave then walks
+// the frames among the 64 in order -- the set bits of the ballot of T != 0,
+// each T fetched with v_readlane -- with the cursor (row, off) and the counters
+// in scalar registers.  A frame's span is known when the next frame is placed,
+// so each step stores the record of the frame before it, and that frame's
+// row's length word when the row changed, from lane 0; the last frame's follow
+// the loop.  Every row below the layout's row count holds a frame, so the
+// length words of rows [min(rows, maxRows), maxRows) are the ones left to zero,
+// 64 per store.  The walk is serial: one step per frame, a few tens of scalar
+// instructions and at most two one-lane stores, at most 65535 steps a job;
+// jobs run side by side.  No LDS, no atomics, no scratch.
+__global__ __launch_bounds__(64 * kDeliverWaves) void k_plan(const PackJob* __restrict__ jobs, uint32_t jobCount,
+                                                             const PackItem* __restrict__ items,
+                                                             PlanRec* __restrict__ plan)
+{
+    const uint32_t ji = __builtin_amdgcn_readfirstlane(blockIdx.x * kDeliverWaves + (threadIdx.x >> 6));
+    if (ji >= jobCount)
+        return;
+    const uint32_t lane = threadIdx.x & 63;
+    const PackJob jb = jobs[ji];
+    const uint64_t stride = (uint64_t)jb.stride16 << 4;
+    const uint64_t planBase = (uint64_t)(uintptr_t)(plan + jb.first);
+    uint32_t row = 0, frames = 0, written = 0, unfit = 0;
+    uint64_t off = 0;
+    bool open = false;   // a frame was placed whose record is not stored yet
+    uint32_t prevK = 0, prevRow = 0;
+    uint64_t prevOff = 0, prevEnd = 0;
+    for (uint32_t b = 0; b < jb.count; b += 64) {
+        const uint32_t k = b + lane;
+        uint32_t T = 0;
+        bool present = false;
+        if (k < jb.count) {
+            const PackItem it = items[jb.first + k];
+            present = it.src != 0;
+            if (present && it.cap != 0) {
+                uint32_t hs, n;
+                const uint32_t pf = relay_sizes(*reinterpret_cast<const GMEM uint32_t*>(it.src), it.cap, stride, &hs, &n);
+                T = pf ? pf + 7u + n : 0u;
+            }
+            if (T == 0)
+                st16(planBase + (uint64_t)k * sizeof(PlanRec), make_uint4(0, 0, 0, 0));
+        }
+        unfit += (uint32_t)__popcll(__ballot(present && T == 0));
+        uint64_t m = __ballot(T != 0);
+        while (m) {   // (wave-uniform)
+            const uint32_t j = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(m));
+            m &= m - 1;
+            const uint32_t Tj = __builtin_amdgcn_readlane(T, j);
+            if (off + Tj > stride) {
+                ++row;
+                off = 0;
+            }
+            if (open && lane == 0) {
+                const uint64_t span = (prevRow == row ? off : stride) - prevOff;
+                st16(planBase + (uint64_t)prevK * sizeof(PlanRec),
+                     make_uint4(prevRow, (uint32_t)(prevOff >> 4), (uint32_t)(span >> 4),
+                                prevRow < jb.maxRows ? kPlanWrite : 0u));
+                if (prevRow != row && prevRow < jb.maxRows)
+                    *reinterpret_cast<GMEM uint32_t*>(jb.lens + (uint64_t)prevRow * 4) = (uint32_t)prevEnd;
+            }
+            written += row < jb.maxRows ? 1u : 0u;
+            ++frames;
+            open = true;
+            prevK = b + j;
+            prevRow = row;
+            prevOff = off;
+            prevEnd = off + Tj;
+            off = (prevEnd + 15) & ~(uint64_t)15;
+        }
+    }
+    if (open && lane == 0) {
+        st16(planBase + (uint64_t)prevK * sizeof(PlanRec),
+             make_uint4(prevRow, (uint32_t)(prevOff >> 4), (uint32_t)((stride - prevOff) >> 4),
+                        prevRow < jb.maxRows ? kPlanWrite : 0u));
+        if (prevRow < jb.maxRows)
+            *reinterpret_cast<GMEM uint32_t*>(jb.lens + (uint64_t)prevRow * 4) = (uint32_t)prevEnd;
+    }
+    const uint32_t rows = frames ? row + 1 : 0;
+    for (uint64_t r = (uint64_t)(rows < jb.maxRows ? rows : jb.maxRows) + lane; r < jb.maxRows; r += 64)
+        *reinterpret_cast<GMEM uint32_t*>(jb.lens + r * 4) = 0;
+    if (lane == 0)
+        st16(jb.info, make_uint4(rows, written, unfit, frames - written));
+}
+
+// k_pack: k_relay's grid and copy -- one wave per (item, 8 KiB chunk of its
+// span), lane L of each 1 KiB tile writing span bytes [16L, 16L+16) with one
+// 16-byte store, the header merged into lane 0 of tile 0 in registers, the
+// payload byte-shifted with v_alignbyte_b32, zeros from the frame's end to the
+// span's end -- with dst = rows + row * stride + 16 * off16 and the span in
+// place of the row, both from the item's plan record; an item without
+// kPlanWrite is left alone.  The source shift is that of k_relay: the symbol
+// and dst are both 16-byte aligned (rows, stride and the offset are multiples
+// of 16), so span byte 0 lines up with src + hs - hf, hs - hf in [-10, -4], the
+// shift is 6..12 and the three cases of q are the ones that occur.  The plan
+// admitted the frame under the row's stride and a span holds its frame, so
+// the test against the span passes for every record k_plan flagged; were the
+// symbol to differ from what k_plan read, the span would be zeroed as k_relay
+// zeroes a row.  No LDS, no atomics, no scratch.
+__global__ __launch_bounds__(64 * kDeliverWaves) void k_pack(const PackJob* __restrict__ jobs,
+                                                             const PackItem* __restrict__ items,
+                                                             const PlanRec* __restrict__ plan, uint32_t count)
+{
+    const uint32_t ii = __builtin_amdgcn_readfirstlane(blockIdx.x * kDeliverWaves + (threadIdx.x >> 6));
+    if (ii >= count)
+        return;
+    const uint32_t lane = threadIdx.x & 63;
+    const PlanRec pr = plan[ii];
+    if (!(pr.flags & kPlanWrite))   // (uniform)
+        return;
+    const PackItem it = items[ii];
+    const PackJob jb = jobs[it.job];
+    const uint64_t span = (uint64_t)pr.span16 << 4;
+    const uint64_t dst = jb.rows + (uint64_t)pr.row * ((uint64_t)jb.stride16 << 4) + ((uint64_t)pr.off16 << 4);
+    uint32_t hs = 0, hf = 0, n = 0;
+    uint32_t h0 = 0, h1 = 0, h2 = 0;   // the frame header, little-endian dwords
+    {
+        const uint32_t w = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const GMEM uint32_t*>(it.src));
+        const uint32_t pf = relay_sizes(w, it.cap, span, &hs, &n);
+        if (pf) {
+            const uint32_t Lf = n + 7u;
+            const uint32_t pre = pf == 1   ? Lf
+                                 : pf == 2 ? (0x80u | (Lf >> 8)) | ((Lf & 0xffu) << 8)
+                                 : pf == 3 ? (0xC0u | (Lf >> 16)) | (((Lf >> 8) & 0xffu) << 8) | ((Lf & 0xffu) << 16)
+                                           : (0xE0u | (Lf >> 24)) | (((Lf >> 16) & 0xffu) << 8) |
+                                                 (((Lf >> 8) & 0xffu) << 16) | ((Lf & 0xffu) << 24);
+            hf = pf + 7u;
+            // type 0, flow and PacketNum as 56 bits behind the prefix
+            const uint64_t body = ((uint64_t)(it.flow & 0xffffffu) << 8) | ((uint64_t)(it.packetNum & 0xffffffu) << 32);
+            const uint32_t s = 8u * pf;   // 8..32
+            const uint64_t lo = (uint64_t)pre | (body << s);
+            h0 = (uint32_t)lo;
+            h1 = (uint32_t)(lo >> 32);
+            h2 = (uint32_t)(body >> (64u - s));
+        }
+    }
+    const uint64_t total = (uint64_t)hf + n;   // span bytes in use
+    const uint64_t src = it.src + hs;
+    const uint64_t base = src - hf;
+    const unsigned sh = (unsigned)(base & 15u);   // 6..12 (0 for a zeroed span: nothing is loaded)
+    const unsigned q = sh >> 2, r = sh & 3;
+    const uint64_t srcEnd = src + n;
+    const uint64_t step = (uint64_t)gridDim.y * kIngestChunkBytes;
+    for (uint64_t c0 = (uint64_t)blockIdx.y * kIngestChunkBytes; c0 < span; c0 += step) {
+        const uint64_t c1 = c0 + kIngestChunkBytes < span ? c0 + kIngestChunkBytes : span;
+        for (uint64_t t = c0; t < c1; t += 2 * kTileBytes) {
+            uint4 out[2];
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                out[u] = make_uint4(0, 0, 0, 0);
+                if (p >= total)   // the zero fill: nothing to load
+                    continue;
+                const uint64_t a = (base + p) & ~(uint64_t)15;
+                const uint4 lo = (a < srcEnd && a + 16 > src) ? ld16(a) : make_uint4(0, 0, 0, 0);
+                const uint4 hi = a + 16 < srcEnd ? ld16(a + 16) : make_uint4(0, 0, 0, 0);
+                const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                switch (q) {   // wave-uniform; 1..3 for a span in use
+                case 1:
+                    out[u] = make_uint4(pick(w, 1, r, 0), pick(w, 1, r, 1), pick(w, 1, r, 2), pick(w, 1, r, 3));
+                    break;
+                case 2:
+                    out[u] = make_uint4(pick(w, 2, r, 0), pick(w, 2, r, 1), pick(w, 2, r, 2), pick(w, 2, r, 3));
+                    break;
+                default:
+                    out[u] = make_uint4(pick(w, 3, r, 0), pick(w, 3, r, 1), pick(w, 3, r, 2), pick(w, 3, r, 3));
+                    break;
+                }
+            }
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                if (p >= span)
+                    continue;
+                uint4 v = out[u];
+                if (p == 0) {   // the frame header (8..11 bytes) over source bytes
+                    const uint32_t m0 = byte_mask((int)hf), m1 = byte_mask((int)hf - 4), m2 = byte_mask((int)hf - 8);
+                    v.x = (v.x & ~m0) | (h0 & m0);
+                    v.y = (v.y & ~m1) | (h1 & m1);
+                    v.z = (v.z & ~m2) | (h2 & m2);
+                }
+                if (p + 16 > total)
+                    v = mask16(v, p < total ? (int)(total - p) : 0);
+                st16(dst + p, v);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Row scan (k_scan, ops.h RowHead)
 //
 // The way in for frame rows that exist only in device memory: one lane per
@@ -4732,6 +4959,26 @@ void be_launch_relay(const RelayItem* items, uint32_t count, uint32_t maxStride)
         std::min(kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxStride + kIngestChunkBytes - 1) / kIngestChunkBytes)));
     hipLaunchKernelGGL(k_relay, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
                        g_stream, items, count);
+}
+
+void be_launch_pack(const PackJob* jobs, uint32_t jobCount, const PackItem* items, uint32_t count, PlanRec* plan,
+                    uint32_t maxStride)
+{
+    if (jobCount == 0)
+        return;
+    {
+        Timed t(kBePlan);
+        hipLaunchKernelGGL(k_plan, dim3((jobCount + kDeliverWaves - 1) / kDeliverWaves), dim3(64 * kDeliverWaves), 0,
+                           g_stream, jobs, jobCount, items, plan);
+    }
+    if (count == 0)   // (jobs without items: their length words and info records were all there is)
+        return;
+    Timed t(kBePack);
+    // (the grid of be_launch_deliver: a span is at most a row)
+    const uint32_t chunks =
+        std::min(kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxStride + kIngestChunkBytes - 1) / kIngestChunkBytes)));
+    hipLaunchKernelGGL(k_pack, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
+                       g_stream, jobs, items, (const PlanRec*)plan, count);
 }
 
 void be_launch_exec(const void* stream, const ExecItem* items, uint32_t count, uint64_t* acct,

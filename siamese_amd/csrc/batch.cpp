@@ -429,6 +429,27 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_frames(SgpuDecoder decoder, un
     return r;
 }
 
+SIAMESE_EXPORT SiameseResult sgpu_decoder_pack_frames(SgpuDecoder decoder, unsigned flow, unsigned firstPacketNum,
+                                                      unsigned count, void* deviceDst, size_t stride, unsigned maxRows,
+                                                      unsigned* deviceLens, unsigned* deviceInfo,
+                                                      SiameseResult* results, unsigned* queuedOut)
+{
+    if (queuedOut)
+        *queuedOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, lens = (uint64_t)(uintptr_t)deviceLens;
+    const uint64_t info = (uint64_t)(uintptr_t)deviceInfo;
+    // (frame_rows_ok on maxRows: the rows and length words are the caller's whatever the packet count)
+    if (!decoder || BD(decoder)->core.ge_pending() || !frame_rows_ok(maxRows, dst, stride, lens) || !info ||
+        (info & 15u) != 0 || flow > kFrameMaxFlow || firstPacketNum > SIAMESE_PACKET_NUM_MAX || count > kPackMaxItems)
+        return Siamese_InvalidInput;
+    unsigned queued = 0;
+    const SiameseResult r = BD(decoder)->core.pack_frames(firstPacketNum, count, flow, dst, (uint64_t)stride, maxRows,
+                                                          lens, info, results, &queued);
+    if (queuedOut)
+        *queuedOut = queued;
+    return r;
+}
+
 SIAMESE_EXPORT SiameseResult sgpu_decode_deferred(SgpuDecoder decoder, SiameseOriginalPacket* out,
                                                   unsigned capacity, unsigned* countOut)
 {
@@ -889,14 +910,14 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[26] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[27] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
                             s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide,
                             s.delivers,   s.frames,      s.scans,      Engine::global()->walks(),
-                            s.relays};
-    for (unsigned k = 0; k < count && k < 26; ++k)
+                            s.relays,     Engine::global()->packs()};
+    for (unsigned k = 0; k < count && k < 27; ++k)
         out[k] = v[k];
 }
 

@@ -2799,6 +2799,44 @@ SiameseResult DecoderCore::deliver_frames(unsigned firstNum, unsigned count, uns
     return Siamese_Success;
 }
 
+SiameseResult DecoderCore::pack_frames(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst, uint64_t stride,
+                                       unsigned maxRows, uint64_t lens, uint64_t info, SiameseResult* results,
+                                       unsigned* queued)
+{
+    *queued = 0;
+    settle();
+    if (dead())
+        return Siamese_Disabled;
+    // deliver_frames' two passes: the row a frame lands in is the device's to
+    // decide, what fits a row is the same test
+    const unsigned e0 = column_to_element(firstNum);
+    unsigned e = e0;
+    for (unsigned k = 0; k < count; ++k, e = (e + 1) % kColumnPeriod)
+        if (e < count_) {
+            const DecSlot& s = slot(e);
+            if (s.bytes != 0 && !s.pending && !relay_fits(s.header, s.bytes - s.header, s.bytes, stride))
+                return Siamese_InvalidInput;
+        }
+    std::vector<PackItem> items(count);
+    e = e0;
+    for (unsigned k = 0; k < count; ++k, e = (e + 1) % kColumnPeriod) {
+        const DecSlot* s = e < count_ ? &slot(e) : nullptr;
+        const bool present = s && s->bytes != 0;
+        PackItem& it = items[k];
+        it.src = present ? s->buf.addr() : 0;
+        it.cap = present ? s->bytes : 0;
+        it.flow = flow;
+        it.packetNum = (firstNum + k) & SIAMESE_PACKET_NUM_MAX;
+        it.job = 0;
+        if (results)
+            results[k] = present ? Siamese_Success : Siamese_NeedMoreData;
+        if (present)
+            ++*queued;
+    }
+    prog_.pack(items.data(), count, dst, stride, maxRows, lens, info);
+    return Siamese_Success;
+}
+
 SiameseResult DecoderCore::decode_deferred(SiameseOriginalPacket* out, unsigned capacity, unsigned* countOut)
 {
     settle();

@@ -148,6 +148,15 @@ public:
     /// known length plus its frame header exceeds the stride.
     SiameseResult deliver_frames(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst, uint64_t stride,
                                  uint64_t lens, SiameseResult* results, unsigned* queued);
+    /// sgpu_decoder_pack_frames: deliver_frames' frames, several to a row of
+    /// dst[0, maxRows) by the packer's rule (encoder.h pack_frames), laid out
+    /// on the device from the lengths it reads (Program::pack, frames.h
+    /// pack_plan): lens gets maxRows words, info four.  One item per packet of
+    /// the range, absent ones included.  InvalidInput, with nothing queued,
+    /// when a packet's known length plus its frame header exceeds the stride.
+    SiameseResult pack_frames(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst, uint64_t stride,
+                              unsigned maxRows, uint64_t lens, uint64_t info, SiameseResult* results,
+                              unsigned* queued);
     /// Host-memory recovery packet (drop-in API).
     SiameseResult add_recovery(const SiameseRecoveryPacket& packet);
     /// Device-resident recovery packet (batch API).

@@ -120,6 +120,7 @@ void ProgramBody::clear()
     ndeliver = 0;   // (the items' vector keeps its elements: not touched here)
     nframe = 0;
     nrelay = 0;
+    npackjob = npack = 0;
     gateOpen = false;
 }
 
@@ -926,6 +927,31 @@ void Program::relay(uint64_t src, uint32_t cap, uint32_t flow, uint32_t packetNu
     b_->relays[b_->nrelay++] = it;
 }
 
+void Program::pack(const PackItem* items, uint32_t count, uint64_t rows, uint64_t stride, uint32_t maxRows,
+                   uint64_t lens, uint64_t info)
+{
+    touch();
+    PackJob jb;
+    jb.rows = rows;
+    jb.lens = lens;
+    jb.info = info;
+    jb.first = b_->npack;
+    jb.count = count;
+    jb.stride16 = (uint32_t)(stride >> 4);
+    jb.maxRows = maxRows;
+    if (b_->packs.size() < (size_t)b_->npack + count)
+        b_->packs.resize((size_t)b_->npack + count);
+    for (uint32_t k = 0; k < count; ++k) {
+        PackItem& it = b_->packs[b_->npack + k];
+        it = items[k];
+        it.job = b_->npackjob;
+    }
+    b_->npack += count;
+    if (b_->npackjob == b_->packJobs.size())
+        b_->packJobs.emplace_back();
+    b_->packJobs[b_->npackjob++] = jb;
+}
+
 // ---------------------------------------------------------------------------
 // Shard queues
 
@@ -1476,6 +1502,10 @@ struct Batch
     uint32_t maxFrameStride = 0;           // ... their longest row, as maxDeliverStride (k_frame's grid)
     size_t oRelay = 0, nRelay = 0;         // relay items of every body (ops.h RelayItem)
     uint32_t maxRelayStride = 0;           // ... their longest row, as maxDeliverStride (k_relay's grid)
+    size_t oPackJob = 0, nPackJob = 0;     // pack jobs of every body (ops.h PackJob)
+    size_t oPack = 0, nPack = 0;           // ... and their items (ops.h PackItem)
+    size_t oPlan = 0;                      // ... k_plan's records: device side only, behind the upload
+    uint32_t maxPackStride = 0;            // ... the jobs' longest row, as maxDeliverStride (k_pack's grid)
     size_t oCopy = 0;                      // the download copy list (BeCopy records)
     uint64_t wideBase = 0;                 // this submission's k_ldpc scratch: bytes into the ring
     bool wideGated = false;                // k_ldpc items of gated ops: the launches take the gate
@@ -2220,12 +2250,15 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     size_t nDeliver = 0;   // delivery items of every body
     size_t nFrame = 0;     // frame items of every body
     size_t nRelay = 0;     // relay items of every body
+    size_t nPackJob = 0, nPack = 0;   // pack jobs and items of every body
     for (int g = 0; g < 2; ++g)
         for (size_t pi = 0; pi < bt.bodies[g].size(); ++pi) {
             const ProgramBody* p = bt.bodies[g][pi];
             nDeliver += p->ndeliver;   // (beside nges: no line of the body this pass does not read anyway)
             nFrame += p->nframe;
             nRelay += p->nrelay;
+            nPackJob += p->npackjob;
+            nPack += p->npack;
             for (size_t k = 0; k < p->nges; ++k) {
                 const ProgramBody::PendingGe& ge = p->ges[k];
                 GeDesc d;
@@ -2262,6 +2295,8 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     bt.nDeliver = nDeliver;
     bt.nFrame = nFrame;
     bt.nRelay = nRelay;
+    bt.nPackJob = nPackJob;
+    bt.nPack = nPack;
 
     constexpr size_t kIngestChunk = SGPU_INGEST_CHUNK;
     size_t nIngest = 0, stageBytes = 0, nIngBlocks = 0;
@@ -2332,6 +2367,11 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     // the relay items, likewise (one k_relay launch beside them)
     bt.oRelay = off;
     off = align16(off + nRelay * sizeof(RelayItem));
+    // the pack jobs and their items (k_plan and k_pack beside them)
+    bt.oPackJob = off;
+    off = align16(off + nPackJob * sizeof(PackJob));
+    bt.oPack = off;
+    off = align16(off + nPack * sizeof(PackItem));
     // the download copy list (the counters and results, then every range)
     size_t nDownloads = 0;
     for (const Shard::Queues& q : bt.queues)
@@ -2339,8 +2379,11 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     bt.oCopy = off;
     off = align16(off + (nDownloads + 1) * sizeof(BeCopy));
     bt.upBytes = off;
+    // k_plan's records lie behind the upload in its device copy: written and
+    // read on the device only, never uploaded
+    bt.oPlan = off;
     if (bt.upBytes)
-        ensure_up(xs, bt.upBytes);
+        ensure_up(xs, bt.upBytes + nPack * sizeof(PlanRec));
     // A small upload is not copied: the kernels read it from the pinned
     // buffer over the bus (zero-copy), which skips a copy and its hand-off
     // on the latency-bound paths (SIAMESE_AMD_ZEROCOPY_UP bytes at most,
@@ -2568,6 +2611,29 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
             }
         bt.maxRelayStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
     }
+    if (nPackJob) {
+        PackJob* pj = (PackJob*)(up + bt.oPackJob);
+        PackItem* pi = (PackItem*)(up + bt.oPack);
+        uint32_t max16 = 0, jobBase = 0, itemBase = 0;
+        for (int g = 0; g < 2; ++g)
+            for (const ProgramBody* p : bt.bodies[g]) {
+                if (p->npackjob == 0)
+                    continue;
+                // (a body's indices become the launch's)
+                for (uint32_t k = 0; k < p->npackjob; ++k) {
+                    pj[jobBase + k] = p->packJobs[k];
+                    pj[jobBase + k].first += itemBase;
+                    max16 = std::max(max16, pj[jobBase + k].stride16);
+                }
+                for (uint32_t k = 0; k < p->npack; ++k) {
+                    pi[itemBase + k] = p->packs[k];
+                    pi[itemBase + k].job += jobBase;
+                }
+                jobBase += p->npackjob;
+                itemBase += p->npack;
+            }
+        bt.maxPackStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
+    }
 
     // download area: the byte counters (kAcctBytes), the solve results, then
     // each requested range
@@ -2599,7 +2665,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
 
     st.flushes = 1;
     st.launches = phases.size() + (nIngest ? 1 : 0) + (gdescs.empty() ? 0 : 1) + (nDeliver ? 1 : 0) +
-                  (nFrame ? 1 : 0) + (nRelay ? 1 : 0);
+                  (nFrame ? 1 : 0) + (nRelay ? 1 : 0) + (nPackJob ? 1 : 0) + (nPack ? 1 : 0);
     st.delivers = nDeliver;
     st.frames = nFrame;
     st.relays = nRelay;
@@ -2730,6 +2796,14 @@ void Engine::launch_batch(Batch& bt)
     // submission is forwarded from its final bytes, its length prefix included
     if (bt.nRelay)
         be_launch_relay((const RelayItem*)(bt.upBase + bt.oRelay), (uint32_t)bt.nRelay, bt.maxRelayStride);
+    // ... and its pack jobs, on the same terms: k_plan reads the lengths where
+    // the solve left them, k_pack copies by the plan it wrote
+    if (bt.nPackJob) {
+        packs_.fetch_add(bt.nPack, std::memory_order_relaxed);
+        be_launch_pack((const PackJob*)(bt.upBase + bt.oPackJob), (uint32_t)bt.nPackJob,
+                       (const PackItem*)(bt.upBase + bt.oPack), (uint32_t)bt.nPack, (PlanRec*)(xs.upDev + bt.oPlan),
+                       bt.maxPackStride);
+    }
     // the counters and solve results, then the downloads, in one call (one
     // kernel when small; its range list was laid out with the upload: a
     // drop-in submission carries a range per application call)

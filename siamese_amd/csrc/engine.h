@@ -358,6 +358,15 @@ struct ProgramBody
     /// rows (ops.h RelayItem), run by the submission's one k_relay launch
     /// beside k_deliver's.  nrelay in use (capacity is kept).
     std::vector<RelayItem> relays;
+    /// A decoder's packets to forward as wire frames packed several to a row
+    /// (ops.h PackJob, PackItem): one job per Program::pack call, its items
+    /// behind those of the job before; first and job are relative to this
+    /// body until assembly.  Run by the submission's k_plan and k_pack
+    /// launches beside k_deliver's.  npackjob and npack in use (capacity is
+    /// kept).
+    std::vector<PackJob> packJobs;
+    std::vector<PackItem> packs;
+    uint32_t npackjob = 0, npack = 0;
     void lc_seal();                     // seals the open OP_LINCOMBS batch
     /// Move the segment's last op (an OP_LINCOMB) into the open batch, or
     /// seal the batch first when they are not independent.
@@ -367,7 +376,7 @@ struct ProgramBody
 
     bool empty() const
     {
-        return nges == 0 && ndeliver == 0 && nframe == 0 && nrelay == 0 &&
+        return nges == 0 && ndeliver == 0 && nframe == 0 && nrelay == 0 && npackjob == 0 &&
                (nsegs == 0 ||
                 (nsegs == 1 && segs[0].ops.empty() && copies.empty() && lcb.items.empty() && !rb.open));
     }
@@ -547,6 +556,16 @@ public:
     /// submission.
     void relay(uint64_t src, uint32_t cap, uint32_t flow, uint32_t packetNum, uint64_t dst, uint64_t lenOut,
                uint64_t stride);
+
+    /// Queue one pack job (ops.h PackJob) and its items: items[k] holds packet
+    /// k's symbol, capacity, flow and PacketNum (src = 0: absent; job is set
+    /// here).  The device lays the frames out in rows[0, maxRows) of `stride`
+    /// bytes by the packer's rule and writes lens[0, maxRows) and the four
+    /// words at info (k_plan, k_pack).  Ordered as deliver()'s items.  A job
+    /// without items still zeroes its length words and info record, and a
+    /// program whose only work is pack jobs still makes a submission.
+    void pack(const PackItem* items, uint32_t count, uint64_t rows, uint64_t stride, uint32_t maxRows, uint64_t lens,
+              uint64_t info);
 
     bool empty() const { return !b_ || b_->empty(); }
 
@@ -885,9 +904,13 @@ private:
     // rows scanned by the packed scan, counted when the scan is queued (sgpu_engine_stats_ex [24]); kept
     // here, behind every other member, and not in EngineStats, whose size every submission's counters share
     std::atomic<uint64_t> walks_{0};
+    // pack items queued (sgpu_decoder_pack_frames), counted when their submission is launched
+    // (sgpu_engine_stats_ex [26]); here for the same reason
+    std::atomic<uint64_t> packs_{0};
 
 public:
     uint64_t walks() const { return walks_.load(std::memory_order_relaxed); }
+    uint64_t packs() const { return packs_.load(std::memory_order_relaxed); }
 };
 
 /// Per-host-thread engine state.  Only its owning thread touches it between

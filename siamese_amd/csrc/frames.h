@@ -260,4 +260,70 @@ inline void relay_row(const uint8_t* sym, uint32_t cap, uint32_t flow, uint32_t 
     *len = hf + n;
 }
 
+/// What k_plan computes for one job (ops.h PackJob): syms[k] is item k's symbol
+/// (null: absent), of which caps[k] bytes may be read.  Item k is a frame of
+/// T = hf + n bytes when relay_row would fill a row of `stride` bytes from it,
+/// and takes no space otherwise.  The frames are laid out in item order by the
+/// packer's rule (encoder.h pack_frames): a cursor (row, off) starts at (0, 0);
+/// a frame with off + T > stride moves to (row + 1, 0); it is placed at off and
+/// off becomes align16(off + T).  recs[k] gets the frame's row, its offset and
+/// its span (to the next frame of the row, or to the row's end) in 16-byte
+/// units, and kPlanWrite when row < maxRows; an item that is no frame gets a
+/// zero record.  lens[r], r < maxRows, is the end of row r's last frame, zero
+/// for a row without one.  info = {rows the layout needs, frames with
+/// kPlanWrite, present items that do not fit, frames without kPlanWrite}.
+/// k_pack then is relay_row(sym, cap, flow, packetNum, rows + row * stride +
+/// 16 * off16, 16 * span16, ...) for every record with kPlanWrite.  Reads only
+/// syms[k][0, min(caps[k], 4)), writes only recs[0, count), lens[0, maxRows)
+/// and info[0, 4).
+inline void pack_plan(const uint8_t* const* syms, const uint32_t* caps, uint32_t count, uint64_t stride,
+                      uint32_t maxRows, PlanRec* recs, uint32_t* lens, uint32_t* info)
+{
+    uint64_t row = 0, off = 0;
+    uint32_t frames = 0, written = 0, unfit = 0;
+    uint32_t prev = count;   // the last frame placed: its span is still open
+    uint64_t prevOff = 0, prevEnd = 0;
+    for (uint32_t r = 0; r < maxRows; ++r)
+        lens[r] = 0;
+    for (uint32_t k = 0; k < count; ++k) {
+        std::memset(&recs[k], 0, sizeof(PlanRec));
+        if (!syms[k])
+            continue;
+        unsigned length = 0;
+        const int h = read_length_prefix(syms[k], caps[k] < 4 ? caps[k] : 4u, &length);
+        if (h < 1 || !relay_fits((unsigned)h, length, caps[k], stride)) {
+            ++unfit;
+            continue;
+        }
+        const uint64_t T = (uint64_t)frame_header_bytes(kFrameOriginal, length) + length;
+        if (off + T > stride) {   // (never at off = 0: T <= stride)
+            ++row;
+            off = 0;
+        }
+        if (prev != count) {
+            recs[prev].span16 = (uint32_t)(((recs[prev].row == row ? off : stride) - prevOff) >> 4);
+            if (recs[prev].row != row && recs[prev].row < maxRows)
+                lens[recs[prev].row] = (uint32_t)prevEnd;
+        }
+        recs[k].row = (uint32_t)row;
+        recs[k].off16 = (uint32_t)(off >> 4);
+        recs[k].flags = row < maxRows ? kPlanWrite : 0;
+        written += row < maxRows;
+        ++frames;
+        prev = k;
+        prevOff = off;
+        prevEnd = off + T;
+        off = (off + T + 15) & ~(uint64_t)15;
+    }
+    if (prev != count) {
+        recs[prev].span16 = (uint32_t)((stride - prevOff) >> 4);
+        if (recs[prev].row < maxRows)
+            lens[recs[prev].row] = (uint32_t)prevEnd;
+    }
+    info[0] = frames ? (uint32_t)row + 1 : 0;
+    info[1] = written;
+    info[2] = unfit;
+    info[3] = frames - written;
+}
+
 } // namespace sgpu

@@ -473,6 +473,59 @@ struct RelayItem
 static_assert(sizeof(RelayItem) == 40, "RelayItem layout");
 /// k_relay's grid is k_deliver's too.
 
+/// A decoder's packets forwarded as originals' wire frames, several to a row
+/// (k_plan and k_pack, sgpu_decoder_pack_frames).  One PackJob per call, one
+/// PackItem per packet of its range, in packet order; k_plan writes one PlanRec
+/// per item into scratch of the submission, k_pack reads it.
+///
+/// An item's frame is RelayItem's: hs, n and hf from the symbol's first bytes,
+/// T = hf + n when it fits (frames.h relay_fits, with the job's stride), T = 0
+/// for an absent packet (src = 0) or one that does not fit.  k_plan walks the
+/// packer's cursor rule over the job's T in item order (frames.h pack_plan: a
+/// frame with off + T > stride opens the next row, is placed at off, and off
+/// becomes align16(off + T)) and gives every frame its row, its offset and its
+/// span: the bytes up to the next frame of the row, or to the row's end.  It
+/// writes the job's maxRows length words (the end of the row's last frame; zero
+/// for a row without one) and info = {rows needed, frames written, present
+/// packets that do not fit, frames dropped because row >= maxRows}.  k_pack
+/// writes dst[0, span) of every frame flagged kPlanWrite, dst = rows +
+/// row * stride + 16 * off16, as relay_row writes a row of span bytes.  Nothing
+/// else is written; only aligned 16-byte words holding a byte of
+/// [src, src + cap) are read.
+struct PackItem
+{
+    uint64_t src;        // the symbol (0: absent)
+    uint32_t cap;        // as DeliverItem.cap
+    uint32_t flow;       // the frame's flow (<= 2^24 - 1)
+    uint32_t packetNum;  // the frame's PacketNum
+    uint32_t job;        // index of the item's PackJob in the launch
+};
+static_assert(sizeof(PackItem) == 24, "PackItem layout");
+struct PackJob
+{
+    uint64_t rows;       // row 0, 16-byte aligned (not read when maxRows = 0)
+    uint64_t lens;       // maxRows uint32 length words, 4-byte aligned
+    uint64_t info;       // four uint32, 16-byte aligned
+    uint32_t first;      // index of the job's first item in the launch
+    uint32_t count;      // its items (<= 65535)
+    uint32_t stride16;   // a row's bytes / 16 (1 .. 2^28)
+    uint32_t maxRows;    // rows and length words the caller owns
+};
+static_assert(sizeof(PackJob) == 40, "PackJob layout");
+struct PlanRec
+{
+    uint32_t row;        // the frame's row
+    uint32_t off16;      // its offset in the row / 16
+    uint32_t span16;     // bytes to the next frame of the row or to the row's end, / 16
+    uint32_t flags;      // kPlanWrite, or 0: not a frame, or a frame of a row >= maxRows
+};
+static_assert(sizeof(PlanRec) == 16, "PlanRec layout");
+constexpr uint32_t kPlanWrite = 1;
+constexpr uint32_t kPackMaxItems = 65535;   // items of one job
+/// k_plan runs one wave per job, kDeliverWaves jobs per workgroup; k_pack's
+/// grid is k_deliver's over the items, the chunk rows sized by the longest
+/// stride (a span is at most a row).
+
 /// What the host needs of one frame row that lives in device memory (k_scan,
 /// sgpu_frames_scan_rows): the layout of SgpuRowHead (include/siamese_gpu.h),
 /// written as eight dwords

@@ -512,6 +512,43 @@ void be_launch_relay(const RelayItem* items, uint32_t count, uint32_t)
     }
 }
 
+// k_plan and k_pack (ops.h PackJob, PackItem, PlanRec): frames.h pack_plan for
+// every job, then relay_row into the span of every record it flagged.
+void be_launch_pack(const PackJob* jobs, uint32_t jobCount, const PackItem* items, uint32_t count, PlanRec* plan,
+                    uint32_t)
+{
+    if (noexec())
+        return;
+    for (uint32_t j = 0; j < jobCount; ++j) {
+        const PackJob& jb = jobs[j];
+        std::vector<const uint8_t*> syms(jb.count);
+        std::vector<uint32_t> caps(jb.count);
+        for (uint32_t k = 0; k < jb.count; ++k) {
+            const PackItem& it = items[jb.first + k];
+            syms[k] = it.src ? P(it.src) : nullptr;
+            caps[k] = it.cap;
+        }
+        std::vector<uint32_t> lens(jb.maxRows);
+        uint32_t info[4];
+        pack_plan(syms.data(), caps.data(), jb.count, (uint64_t)jb.stride16 << 4, jb.maxRows, plan + jb.first,
+                  lens.data(), info);
+        if (jb.maxRows)
+            std::memcpy(P(jb.lens), lens.data(), (size_t)jb.maxRows * 4);
+        std::memcpy(P(jb.info), info, sizeof(info));
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        const PlanRec& pr = plan[i];
+        if (!(pr.flags & kPlanWrite))
+            continue;
+        const PackItem& it = items[i];
+        const PackJob& jb = jobs[it.job];
+        uint32_t lw = 0;   // (the row's length word is the plan's)
+        relay_row(P(it.src), it.cap, it.flow, it.packetNum,
+                  P(jb.rows + (uint64_t)pr.row * ((uint64_t)jb.stride16 << 4) + ((uint64_t)pr.off16 << 4)),
+                  (uint64_t)pr.span16 << 4, &lw);
+    }
+}
+
 static void solve_prefix(const SolveDesc* solves, const SolveRow* rows, const uint8_t* coef,
                             uint32_t* results, uint32_t count, uint64_t* acct)
 {
