@@ -318,16 +318,25 @@ SIAMESE_EXPORT int sgpu_gather_wait(long long ticket);
     datagram:
       [L: byte length of the rest, in the symbol length-prefix format of
           the reference (SiameseSerializers.h:566-593), 1-4 bytes]
-      [type: 1 byte, SGPU_FRAME_ORIGINAL or SGPU_FRAME_RECOVERY]
+      [type: 1 byte, SGPU_FRAME_ORIGINAL, SGPU_FRAME_RECOVERY or SGPU_FRAME_ACK]
       [flow: 3 bytes little-endian, the application's stream id]
       original:  [PacketNum: 3 bytes LE] [payload]
       recovery:  [the recovery packet, its metadata footer included
                   (SiameseSerializers.h:736-800)]
+      ack:       [the acknowledgement message, exactly as sgpu_decoder_ack
+                  wrote it: at least 1 byte, so L >= 5; no upper bound but the
+                  frame format's]
     Frames follow each other directly; a zero byte where a frame would start
     is an empty frame and is skipped (senders pad frames with zeros).
+    Ack frames are taken by the duplex calls alone ("Closing the loop" below):
+    sgpu_frames_parse, sgpu_frames_recv, sgpu_frames_scan_rows,
+    sgpu_frames_scan_packed, sgpu_frames_recv_rows, sgpu_frames_recv_packed,
+    sgpu_frame_header_bytes and sgpu_frame_write_header know two types and call
+    type 2 malformed.
 */
 #define SGPU_FRAME_ORIGINAL 0
 #define SGPU_FRAME_RECOVERY 1
+#define SGPU_FRAME_ACK      2
 
 typedef struct SgpuFrame
 {
@@ -714,6 +723,162 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_pack_frames(SgpuDecoder decoder, unsig
                                                       SiameseResult* results /* host, count, optional */,
                                                       unsigned* queuedOut);
 
+/*
+    Closing the loop: the ARQ half of the codec for batch instances.  The
+    receiver states what it still misses, the sender slides its window on
+    that, learns a round-trip time, and resends what stays missing after its
+    retransmission timeout.  The first five calls are siamese.h's, on batch
+    instances; the others move acknowledgements and retransmissions through
+    device rows like every other packet of this header.
+
+    Threading and dead instances as for the other per-instance calls; none of
+    these calls waits for the GPU.
+*/
+/// siamese_decoder_ack (siamese.h) on a batch decoder: the acknowledgement
+/// message into buffer[0, byteLimit), *usedOut its bytes.  Siamese_InvalidInput
+/// for a null argument, byteLimit < SIAMESE_ACK_MIN_BYTES, or a decoder with a
+/// device matrix job pending; Siamese_NeedMoreData (*usedOut = 0) before the
+/// first packet has arrived.
+SIAMESE_EXPORT SiameseResult sgpu_decoder_ack(SgpuDecoder decoder, void* buffer, unsigned byteLimit,
+                                              unsigned* usedOut);
+/// siamese_encoder_ack on a batch encoder: takes a message sgpu_decoder_ack
+/// wrote; *nextExpectedOut = the first packet the receiver still waits for.
+/// The originals the message releases are recycled under the device pointer
+/// lifetime rule above: after the submission that holds this call.
+SIAMESE_EXPORT SiameseResult sgpu_encoder_acknowledge(SgpuEncoder encoder, const void* buffer, unsigned bytes,
+                                                      unsigned* nextExpectedOut);
+/// siamese_encoder_retransmit on a batch encoder: the next original whose
+/// retransmission timeout has passed (Siamese_NeedMoreData: none now).
+/// out->Data is a device pointer, under the device pointer lifetime rule.
+SIAMESE_EXPORT SiameseResult sgpu_encoder_retransmit(SgpuEncoder encoder, SiameseOriginalPacket* out);
+/// siamese_encoder_stats / siamese_decoder_stats on batch instances
+/// (SiameseEncoderStats_* / SiameseDecoderStats_* indices).
+SIAMESE_EXPORT SiameseResult sgpu_encoder_stats(SgpuEncoder encoder, uint64_t* statsOut, unsigned statsCount);
+SIAMESE_EXPORT SiameseResult sgpu_decoder_stats(SgpuDecoder decoder, uint64_t* statsOut, unsigned statsCount);
+
+/// Host helper: the SGPU_FRAME_ACK frame for `flow` around msg[0, bytes) into
+/// out[0, capacity).  Returns the frame's bytes; 0 for a null pointer, an empty
+/// message, a flow above 2^24-1, a message whose L no prefix can state, or a
+/// frame longer than capacity.
+SIAMESE_EXPORT unsigned sgpu_frame_write_ack(unsigned flow, const void* msg, unsigned bytes, void* out,
+                                             unsigned capacity);
+
+/// Acks out: queue decoder k's acknowledgement (sgpu_decoder_ack with
+/// byteLimit) as an SGPU_FRAME_ACK frame for flows[k] into row k of
+/// caller-owned device rows.  The message is made here, on the host, and rides
+/// in the submission's upload; k_frame places it.  The row contract is the
+/// deliver calls': row k = what sgpu_frame_write_ack(flows[k], message) writes,
+/// then zeros to the row's end, deviceLens[k] = the frame's bytes, in place when
+/// the carrying submission completes; the call never waits.  A decoder that
+/// answers Siamese_NeedMoreData (nothing received yet) gets results[k] =
+/// NeedMoreData, deviceLens[k] = 0 and an untouched row; so does a dead one,
+/// with results[k] = Siamese_Disabled, which the call then returns.  Otherwise
+/// the call returns Siamese_Success, *queuedOut = the frames queued.
+/// Siamese_InvalidInput, with nothing queued: the deliver calls' pointer,
+/// alignment and stride rules; null decoders or flows with count > 0; a null
+/// decoder or one with a device matrix job pending; a flow above 2^24-1;
+/// byteLimit < SIAMESE_ACK_MIN_BYTES; a frame of byteLimit message bytes longer
+/// than stride.
+SIAMESE_EXPORT SiameseResult sgpu_decoders_ack_frames(const SgpuDecoder* decoders, unsigned count,
+                                                      const unsigned* flows, unsigned byteLimit, void* deviceDst,
+                                                      size_t stride, unsigned* deviceLens,
+                                                      SiameseResult* results /* host, optional */,
+                                                      unsigned* queuedOut);
+/// Retransmits out: sgpu_encoder_retransmit until it answers
+/// Siamese_NeedMoreData or maxPackets packets were returned, each queued as an
+/// SGPU_FRAME_ORIGINAL frame for `flow`, packed into MTU-sized rows by
+/// sgpu_encoder_pack_frames' cursor rule with its zero fill and its length
+/// words (deviceLens[r] = 0 and an untouched row for r in [*rowsOut, maxRows)).
+/// packetNumsOut[i] (host, optional, maxPackets entries) = frame i's PacketNum;
+/// *framesOut = the frames queued.  The written rows are valid input for
+/// sgpu_frames_parse and sgpu_frames_scan_packed.
+///
+/// A retransmission restarts its packet's timer, so none is consumed that
+/// cannot be placed: before each one, a frame of the longest original of the
+/// unacknowledged window must still fit the rows that are left; if not, the
+/// call stops and returns Siamese_Success with what it has (call again with
+/// more rows for the rest).  If such a frame does not fit `stride` at all:
+/// Siamese_InvalidInput, nothing consumed.  Also Siamese_InvalidInput, with
+/// nothing queued: sgpu_encoder_pack_frames' pointer, alignment, stride and
+/// flow rules; a null encoder, rowsOut or framesOut.  A disabled encoder
+/// returns Siamese_Disabled.
+SIAMESE_EXPORT SiameseResult sgpu_encoder_retransmit_frames(SgpuEncoder encoder, unsigned flow, unsigned maxPackets,
+                                                            void* deviceDst, size_t stride, unsigned maxRows,
+                                                            unsigned* deviceLens,
+                                                            unsigned* packetNumsOut /* host, optional */,
+                                                            unsigned* rowsOut, unsigned* framesOut);
+
+/*
+    Acks (and everything else) in: datagram rows of a bidirectional flow mix
+    originals, recovery packets and acks.  The duplex scan is the packed scan
+    with ack frames accepted, and the whole message of each in a slot:
+
+        bytes  = sgpu_frames_duplex_bytes(count, maxFrames, ackSlots, ackBytes);   // pinned
+        ticket = sgpu_frames_scan_duplex(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, out);
+        sgpu_gather_wait(ticket);
+        sgpu_frames_recv_duplex(decoders, nd, encoders, ne, out, maxFrames, ackSlots, ackBytes, rows, stride,
+                                count, results, nextExpected, &accepted);
+
+    out is sgpu_frames_scan_packed's output unchanged (count * maxFrames
+    SgpuPackedHead records, then count row words) and then, from the next
+    16-byte boundary on (sgpu_frames_duplex_slots(count, maxFrames) bytes into
+    out), count * ackSlots message slots of ackBytes bytes, row k's at slot
+    index k * ackSlots.  ackBytes is a multiple of 16 in 16..1024, ackSlots in
+    1..maxFrames.
+
+    The row's a-th ack frame (a from 0), of D message bytes, has a record with
+    Type = SGPU_FRAME_ACK, PacketNum = a, DataBytes = D, HeaderBytes = its
+    prefix + 4, and zero TailBytes, Head and Tail.  When a < ackSlots, slot a
+    holds the message's first min(D, ackBytes) bytes and zeros after them.  Its
+    Status is SGPU_ROW_OK when it has a slot that holds the whole message;
+    otherwise (D > ackBytes, or a >= ackSlots) it is SGPU_ROW_TRUNCATED and the
+    row word carries SGPU_PACKED_ACKS_DROPPED.  Either way the walk goes on, so
+    the data frames behind the ack are kept.  Slots without an ack are zero.
+*/
+#define SGPU_ROW_TRUNCATED       3            /* an ack record whose message is not (whole) in a slot */
+#define SGPU_PACKED_ACKS_DROPPED 0x20000000u  /* the row has an SGPU_ROW_TRUNCATED record */
+
+/// Bytes of a duplex scan's output (0 for arguments sgpu_frames_scan_duplex refuses).
+SIAMESE_EXPORT size_t sgpu_frames_duplex_bytes(unsigned count, unsigned maxFrames, unsigned ackSlots,
+                                               unsigned ackBytes);
+/// Byte offset of the first message slot in a duplex scan's output.
+SIAMESE_EXPORT size_t sgpu_frames_duplex_slots(unsigned count, unsigned maxFrames);
+/// sgpu_frames_scan_packed for rows that may hold ack frames (one k_ackwalk
+/// launch): the same contract, tickets, arguments and deviceLens rules (the
+/// empty row, the row longer than stride, the end of the walk), the same walk
+/// with type 2 accepted when L > 4, and records for originals and recovery
+/// frames that are byte for byte the packed scan's.  Every record, every row
+/// word and every slot is written by every scan; nothing outside
+/// [row, row + stride) and the row's length word is read.  Returns -1 also for
+/// ackSlots outside 1..maxFrames and ackBytes not a multiple of 16 in 16..1024.
+SIAMESE_EXPORT long long sgpu_frames_scan_duplex(const void* deviceRows, size_t stride, const unsigned* deviceLens,
+                                                 unsigned count, unsigned maxFrames, unsigned ackSlots,
+                                                 unsigned ackBytes, void* pinnedOut);
+/// Host only: sgpu_frames_recv_packed for a duplex scan's output.  Originals
+/// and recovery frames go to decoders[Flow] exactly as there; an ack record
+/// with Status SGPU_ROW_OK goes to sgpu_encoder_acknowledge(encoders[Flow], its
+/// slot, DataBytes), the answer's next expected packet into
+/// nextExpectedOut[k * maxFrames + j] (optional, count * maxFrames entries;
+/// other entries are left alone).  results as in sgpu_frames_recv_packed.
+/// Siamese_InvalidInput for: a truncated ack (it is never handed to an
+/// encoder: cut short, a message states a different loss list); a flow without
+/// an encoder; an ack record the scan could not have produced (PacketNum not
+/// the number of ack records before it in its row, DataBytes or the frame
+/// outside its bounds, a Status that disagrees with its slot).  The records,
+/// words and slots are caller data and never trusted: each is copied and
+/// checked before use.  *acceptedOut = the frames handed to a decoder or an
+/// encoder.  decoders (encoders) may be null when decoderCount (encoderCount)
+/// is 0; otherwise arguments are refused as in sgpu_frames_recv_packed and as
+/// in the scan.
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                     const SgpuEncoder* encoders, unsigned encoderCount,
+                                                     const void* heads, unsigned maxFrames, unsigned ackSlots,
+                                                     unsigned ackBytes, const void* deviceRows, size_t stride,
+                                                     unsigned count,
+                                                     SiameseResult* results /* count*maxFrames, optional */,
+                                                     unsigned* nextExpectedOut /* count*maxFrames, optional */,
+                                                     unsigned* acceptedOut);
+
 /// Device timing of flushed work since the last reset (milliseconds).
 SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* totalMs);
 /// Device milliseconds per kernel class since the last sgpu_timing reset,
@@ -725,7 +890,8 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// (sgpu_frames_scan_rows: launched on the gather stream, counted once its
 /// gather has been waited for), [8] k_walk (sgpu_frames_scan_packed,
 /// likewise), [9] k_relay (sgpu_decoder_deliver_frames), [10] k_plan and [11]
-/// k_pack (sgpu_decoder_pack_frames); count entries at most.
+/// k_pack (sgpu_decoder_pack_frames), [12] k_ackwalk (sgpu_frames_scan_duplex,
+/// counted as k_walk is); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -749,7 +915,9 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// rows scanned by sgpu_frames_scan_packed, counted likewise, then [25] the
 /// relay items queued (sgpu_decoder_deliver_frames: counted as [21]), then
 /// [26] the pack items queued (sgpu_decoder_pack_frames: one per packet of the
-/// range, absent ones included); count entries at most.
+/// range, absent ones included), then [27] the rows scanned by
+/// sgpu_frames_scan_duplex, counted as [24], then [28] the ack frames queued
+/// (sgpu_decoders_ack_frames, counted by the call); count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

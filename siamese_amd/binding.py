@@ -80,6 +80,38 @@ def bind_relay_pack_abi(L):
     return L
 
 
+FRAME_ACK = 2
+ROW_TRUNCATED = 3
+PACKED_ACKS_DROPPED = 0x20000000
+
+
+def bind_duplex_abi(L):
+    """Prototypes of the ARQ calls of siamese_gpu.h ("Closing the loop"):
+    acknowledgements and retransmissions on batch instances, their device rows,
+    and the duplex scan that takes rows with ack frames in them."""
+    vp, u, sz, i = ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t, ctypes.c_int
+    bind_packed_abi(L)
+
+    def sig(name, res, args):
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+
+    sig("sgpu_decoder_ack", i, [vp, vp, u, vp])
+    sig("sgpu_encoder_acknowledge", i, [vp, ctypes.c_char_p, u, vp])
+    sig("sgpu_encoder_retransmit", i, [vp, vp])
+    sig("sgpu_encoder_stats", i, [vp, vp, u])
+    sig("sgpu_decoder_stats", i, [vp, vp, u])
+    sig("sgpu_frame_write_ack", u, [u, ctypes.c_char_p, u, vp, u])
+    sig("sgpu_decoders_ack_frames", i, [vp, u, vp, u, vp, sz, vp, vp, vp])
+    sig("sgpu_encoder_retransmit_frames", i, [vp, u, u, vp, sz, u, vp, vp, vp, vp])
+    sig("sgpu_frames_duplex_bytes", sz, [u, u, u, u])
+    sig("sgpu_frames_duplex_slots", sz, [u, u])
+    sig("sgpu_frames_scan_duplex", ctypes.c_longlong, [vp, sz, vp, u, u, u, u, vp])
+    sig("sgpu_frames_recv_duplex", i, [vp, u, vp, u, vp, u, u, u, vp, sz, u, vp, vp, vp])
+    return L
+
+
 class SiameseError(RuntimeError):
     def __init__(self, what, code):
         name = RESULT_NAMES[code] if 0 <= code < 6 else str(code)

@@ -207,6 +207,15 @@ bool be_scan_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint3
 /// without waiting.  rows, stride, lens and the marks are be_scan_rows'.
 bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
                   void* devStage, void* hostOut, void** packed, void** landed);
+/// One k_ackwalk launch on the gather stream (ops.h kRowTruncated): k_walk's
+/// records and row words, and ackSlots message slots of ackBytes bytes per row
+/// from duplex_slots_offset(count, maxFrames) on, into devStage
+/// (duplex_bytes(count, maxFrames, ackSlots, ackBytes), device memory, 16-byte
+/// aligned), then one copy of all of it to hostOut (pinned), without waiting.
+/// rows, stride, lens and the marks are be_scan_rows'.
+bool be_ackwalk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                     uint32_t ackSlots, uint32_t ackBytes, void* devStage, void* hostOut, void** packed,
+                     void** landed);
 /// Block until the device has passed `mark`, then recycle it; false on a
 /// device fault.
 bool be_mark_sync(void* mark);
@@ -214,7 +223,7 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-/// (kBeScan and kBeWalk are bracketed on the gather stream: be_sync waits for a
+/// (kBeScan, kBeWalk and kBeAckWalk are bracketed on the gather stream: be_sync waits for a
 /// bracket of those classes still in flight before it folds it in)
 enum BeKernel
 {
@@ -230,6 +239,7 @@ enum BeKernel
     kBeRelay,
     kBePlan,
     kBePack,
+    kBeAckWalk,
     kBeKernelKinds
 };
 void be_timing_enable(bool on);

@@ -27,6 +27,7 @@
 //                  into caller-owned rows (header, packet, zero tail; opt-in)
 //   k_scan         frame rows in device memory into 32-byte host records
 //   k_walk         rows that hold several frames into one record per frame
+//   k_ackwalk      k_walk with acknowledgement frames, their messages into slots
 //                  (header fields, a recovery packet's head and tail; opt-in)
 //
 // GF(256) multiply by a wave-uniform constant uses three v_perm_b32 byte
@@ -4460,6 +4461,178 @@ __global__ __launch_bounds__(kWalkThreads) void k_walk(uint64_t rows, uint64_t s
 }
 
 // ---------------------------------------------------------------------------
+// Duplex row walk (k_ackwalk, ops.h kRowTruncated)
+//
+// k_walk for the rows of a bidirectional flow (frames.h ack_walk is the
+// statement): the same lane per row and the same cursor, with frames of type
+// 2 accepted.  Their record needs no tail; what the host needs is the whole
+// acknowledgement message, which goes into the row's next message slot behind
+// the row words.  The message starts at any byte of the row and the slot is
+// 16-byte aligned, so the lane streams it: each aligned word of the row is
+// loaded once, the 16 bytes from the message's cursor are the shifted halves of
+// two neighbouring words (k_walk's recombination), the last word is masked to
+// the message's end, and the slot is written in whole 16-byte stores, zeros to
+// its end.  A word is loaded only when a message byte lies in it, and the
+// message ends at or before the row's end: nothing past the row is read.  All
+// output goes to the scan's device staging area and crosses to the host in one
+// copy, so no lane ever stores bytes into host memory.  A message longer than
+// its slot, or an ack after the row's last slot, is reported as truncated and
+// the walk goes on behind it.  No LDS, no atomics.
+
+__global__ __launch_bounds__(kAckWalkThreads) void k_ackwalk(uint64_t rows, uint64_t stride,
+                                                             const uint32_t* __restrict__ lens, uint32_t count,
+                                                             uint32_t maxFrames, uint32_t ackSlots,
+                                                             uint32_t ackBytes, uint64_t out, uint64_t slots)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kAckWalkThreads + threadIdx.x;
+    if (k >= count)
+        return;
+    const uint64_t row = rows + k * stride;
+    const uint64_t rec = out + k * maxFrames * 32;
+    const uint64_t slot0 = slots + k * ackSlots * ackBytes;
+    uint64_t end = lens ? lens[k] : stride;
+    uint32_t n = 0, acks = 0, flags = 0;
+    if (end > stride) {
+        flags = kPackedMalformed;
+        end = 0;
+    }
+    uint64_t at = 0;
+    while (at < end) {
+        const uint64_t wa = at & ~(uint64_t)15;
+        const uint4 A = ld16(row + wa);
+        const uint64_t d0 = pack64(A.x, A.y), d1 = pack64(A.z, A.w);
+        // the word's bytes in [at, end)
+        const int64_t lo = (int64_t)(at - wa), hi = (int64_t)(end - wa);
+        const uint64_t m0 = d0 & low_bytes64(hi) & ~low_bytes64(lo);
+        const uint64_t m1 = d1 & low_bytes64(hi - 8) & ~low_bytes64(lo - 8);
+        if ((m0 | m1) == 0) {
+            at = wa + 16;
+            continue;
+        }
+        const uint32_t s = m0 ? (uint32_t)(__ffsll((long long)m0) - 1) >> 3
+                              : 8u + ((uint32_t)(__ffsll((long long)m1) - 1) >> 3);
+        at = wa + s;
+        if (n == maxFrames) {
+            flags |= kPackedMore;
+            break;
+        }
+        // row bytes [at, at + 16), zero where the next word is not loaded
+        const uint4 B = (s > 4 && wa + 16 < stride) ? ld16(row + wa + 16) : make_uint4(0, 0, 0, 0);
+        const uint64_t d2 = pack64(B.x, B.y), d3 = pack64(B.z, B.w);
+        const uint64_t P = (s & 8u) ? d1 : d0, Q = (s & 8u) ? d2 : d1, R = (s & 8u) ? d3 : d2;
+        const uint32_t sh = 8u * (s & 7u);
+        uint64_t w0 = P >> sh, w1 = Q >> sh;
+        if (sh) {
+            w0 |= Q << (64u - sh);
+            w1 |= R << (64u - sh);
+        }
+        const uint64_t left = end - at;
+        uint32_t L = 0;
+        const int hp = parse_prefix((uint32_t)w0, left < 4 ? (uint32_t)left : 4u, &L);
+        bool ok = hp >= 1 && L >= 1 && (uint64_t)hp + L <= left;
+        uint4 r0 = make_uint4(0, 0, 0, 0), r1 = make_uint4(0, 0, 0, 0);
+        uint32_t total = 0;
+        if (ok) {
+            const uint32_t h = (uint32_t)hp;
+            // row bytes [at + h, at + h + 8): type, flow, then PacketNum or the packet's first bytes
+            const uint64_t x = (w0 >> (8u * h)) | (w1 << (64u - 8u * h));
+            const uint32_t type = (uint32_t)x & 0xffu;
+            const uint32_t inner = type == 0 ? 7u : 4u;
+            const uint32_t flow = (uint32_t)(x >> 8) & 0xffffffu;
+            const uint32_t num = type == 0 ? (uint32_t)(x >> 32) & 0xffffffu : 0u;
+            total = h + L;   // (L < 2^29)
+            ok = type <= 2 && L > inner && num <= 0x3fffffu;
+            if (ok && type == 2) {
+                const uint32_t D = L - inner;
+                uint32_t status = kRowOk;
+                if (acks >= ackSlots || D > ackBytes) {
+                    status = kRowTruncated;
+                    flags |= kPackedAcksDropped;
+                }
+                if (acks < ackSlots) {
+                    // the message is row bytes [p0, fe), fe <= end <= stride; the slot takes [p0, p0 + copy)
+                    const uint32_t copy = D < ackBytes ? D : ackBytes;
+                    const uint64_t p0 = at + h + inner, fe = p0 + copy;
+                    const uint64_t slot = slot0 + (uint64_t)acks * ackBytes;
+                    const uint32_t ms = (uint32_t)p0 & 15u, msh = 8u * (ms & 7u);
+                    uint64_t mw = p0 & ~(uint64_t)15;
+                    uint4 C = mw == wa ? A : ld16(row + mw);   // (mw < fe <= stride)
+                    for (uint32_t o = 0; o < ackBytes; o += 16) {
+                        uint4 v = make_uint4(0, 0, 0, 0);
+                        if (o < copy) {
+                            // the next word only when a message byte lies in it (then mw + 16 < fe <= stride)
+                            const uint4 N = mw + 16 < fe ? ld16(row + mw + 16) : make_uint4(0, 0, 0, 0);
+                            const uint64_t c0 = pack64(C.x, C.y), c1 = pack64(C.z, C.w);
+                            const uint64_t c2 = pack64(N.x, N.y), c3 = pack64(N.z, N.w);
+                            const uint64_t MP = (ms & 8u) ? c1 : c0, MQ = (ms & 8u) ? c2 : c1, MR = (ms & 8u) ? c3 : c2;
+                            uint64_t v0 = MP >> msh, v1 = MQ >> msh;
+                            if (msh) {
+                                v0 |= MQ << (64u - msh);
+                                v1 |= MR << (64u - msh);
+                            }
+                            const int64_t rem = (int64_t)copy - (int64_t)o;
+                            v0 &= low_bytes64(rem);
+                            v1 &= low_bytes64(rem - 8);
+                            v = make_uint4((uint32_t)v0, (uint32_t)(v0 >> 32), (uint32_t)v1, (uint32_t)(v1 >> 32));
+                            C = N;
+                            mw += 16;
+                        }
+                        st16(slot + o, v);
+                    }
+                }
+                r0 = make_uint4((uint32_t)at, status | (type << 8) | ((h + inner) << 16), flow, acks);
+                r1 = make_uint4(D, 0, 0, 0);
+                ++acks;
+            } else if (ok) {
+                const uint32_t D = L - inner;
+                uint32_t head = 0, T = 0;
+                uint64_t tail = 0;
+                if (type == 1) {
+                    head = (uint32_t)(x >> 32) & byte_mask((int)D);
+                    T = D < 8 ? D : 8;
+                    const uint64_t fe = at + total;   // the tail is row bytes [fe - T, fe), fe <= end
+                    const uint64_t s0 = fe - T;
+                    const uint64_t wlo = s0 & ~(uint64_t)15, whi = (fe - 1) & ~(uint64_t)15;   // (whi < stride)
+                    const uint4 a = wlo == wa ? A : ld16(row + wlo);
+                    const uint4 b = whi != wlo ? ld16(row + whi) : make_uint4(0, 0, 0, 0);
+                    const uint32_t ts = (uint32_t)s0 & 15u;
+                    const uint64_t e0 = pack64(a.x, a.y), e1 = pack64(a.z, a.w), e2 = pack64(b.x, b.y);
+                    const uint64_t TA = (ts & 8u) ? e1 : e0, TB = (ts & 8u) ? e2 : e1;
+                    const uint32_t tsh = 8u * (ts & 7u);
+                    uint64_t v = TA >> tsh;
+                    if (tsh)
+                        v |= TB << (64u - tsh);
+                    if (T < 8)
+                        v &= ((uint64_t)1 << (8u * T)) - 1;
+                    tail = v << (8u * (8u - T));   // right-aligned
+                }
+                r0 = make_uint4((uint32_t)at, kRowOk | (type << 8) | ((h + inner) << 16) | (T << 24), flow, num);
+                r1 = make_uint4(D, head, (uint32_t)tail, (uint32_t)(tail >> 32));
+            }
+        }
+        if (!ok) {
+            flags |= kPackedMalformed;
+            break;
+        }
+        st16(rec + (uint64_t)n * 32, r0);
+        st16(rec + (uint64_t)n * 32 + 16, r1);
+        ++n;
+        at += total;
+    }
+    for (uint32_t j = n; j < maxFrames; ++j) {   // every record is written by every scan
+        st16(rec + (uint64_t)j * 32, make_uint4(0, 0, 0, 0));
+        st16(rec + (uint64_t)j * 32 + 16, make_uint4(0, 0, 0, 0));
+    }
+    for (uint32_t a = acks; a < ackSlots; ++a)   // and every slot
+        for (uint32_t o = 0; o < ackBytes; o += 16)
+            st16(slot0 + (uint64_t)a * ackBytes + o, make_uint4(0, 0, 0, 0));
+    *reinterpret_cast<GMEM uint32_t*>(out + (uint64_t)count * maxFrames * 32 + k * 4) = n | flags;
+    if (k + 1 == count)   // the words between the last row word and the first slot
+        for (uint64_t p = out + (uint64_t)count * maxFrames * 32 + (uint64_t)count * 4; p < slots; p += 4)
+            *reinterpret_cast<GMEM uint32_t*>(p) = 0;
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 
 namespace {
@@ -4559,7 +4732,7 @@ void harvest_timing(bool all)
         if (!all && hipEventQuery(ev.b) != hipSuccess)
             break;
         // (a synchronised codec stream says nothing about the gather stream)
-        if (all && (ev.kind == kBeScan || ev.kind == kBeWalk))
+        if (all && (ev.kind == kBeScan || ev.kind == kBeWalk || ev.kind == kBeAckWalk))
             (void)hipEventSynchronize(ev.b);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.a, ev.b);
@@ -5478,6 +5651,38 @@ bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint3
     return true;
 }
 
+bool be_ackwalk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                     uint32_t ackSlots, uint32_t ackBytes, void* devStage, void* hostOut, void** packed,
+                     void** landed)
+{
+    bind_device();
+    *packed = *landed = nullptr;
+    hipEvent_t p = take_mark(), l = take_mark();
+    if (!p || !l) {
+        be_mark_release(p);
+        be_mark_release(l);
+        return false;
+    }
+    {
+        Timed t(kBeAckWalk, g_gatherStream);
+        hipLaunchKernelGGL(k_ackwalk, dim3((count + kAckWalkThreads - 1) / kAckWalkThreads), dim3(kAckWalkThreads), 0,
+                           g_gatherStream, (uint64_t)(uintptr_t)rows, stride, lens, count, maxFrames, ackSlots,
+                           ackBytes, (uint64_t)(uintptr_t)devStage,
+                           (uint64_t)(uintptr_t)devStage + duplex_slots_offset(count, maxFrames));
+    }
+    if (hipEventRecord(p, g_gatherStream) != hipSuccess)
+        return false;
+    *packed = p;
+    if (hipMemcpyAsync(hostOut, devStage, (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes),
+                       hipMemcpyDeviceToHost, g_gatherStream) != hipSuccess ||
+        hipEventRecord(l, g_gatherStream) != hipSuccess) {
+        be_mark_release(l);
+        return false;
+    }
+    *landed = l;
+    return true;
+}
+
 bool be_mark_sync(void* mark)
 {
     bind_device();
@@ -5485,7 +5690,7 @@ bool be_mark_sync(void* mark)
         return false;
     const hipError_t e = hipEventSynchronize(static_cast<hipEvent_t>(mark));
     be_mark_release(mark);
-    if (g_timing && e == hipSuccess)   // (k_scan's and k_walk's bracket ends before its landed mark)
+    if (g_timing && e == hipSuccess)   // (a scan kernel's bracket ends before its landed mark)
         harvest_timing(false);
     if (e != hipSuccess) {
         check(e, "hipEventSynchronize(mark)");

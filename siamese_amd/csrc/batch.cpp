@@ -862,6 +862,218 @@ SIAMESE_EXPORT SiameseResult sgpu_encoder_pack_frames(SgpuEncoder encoder, unsig
                             maxRows, lens, results, rowsOut, framesOut);
 }
 
+// ---- ARQ: acknowledgements and retransmissions (arq.cpp) ---------------------
+
+SIAMESE_EXPORT SiameseResult sgpu_decoder_ack(SgpuDecoder decoder, void* buffer, unsigned byteLimit,
+                                              unsigned* usedOut)
+{
+    if (!decoder || BD(decoder)->core.ge_pending() || !buffer || !usedOut || byteLimit < SIAMESE_ACK_MIN_BYTES)
+        return Siamese_InvalidInput;
+    return BD(decoder)->core.acknowledgement(static_cast<uint8_t*>(buffer), byteLimit, *usedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_encoder_acknowledge(SgpuEncoder encoder, const void* buffer, unsigned bytes,
+                                                      unsigned* nextExpectedOut)
+{
+    if (!encoder || !buffer || bytes < 1 || !nextExpectedOut)
+        return Siamese_InvalidInput;
+    return BE(encoder)->core.acknowledge(static_cast<const uint8_t*>(buffer), bytes, *nextExpectedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_encoder_retransmit(SgpuEncoder encoder, SiameseOriginalPacket* out)
+{
+    if (!encoder || !out)
+        return Siamese_InvalidInput;
+    return BE(encoder)->core.retransmit(*out);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_encoder_stats(SgpuEncoder encoder, uint64_t* statsOut, unsigned statsCount)
+{
+    if (!encoder || !statsOut || statsCount <= 0)
+        return Siamese_InvalidInput;
+    return BE(encoder)->core.stats(statsOut, statsCount);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_decoder_stats(SgpuDecoder decoder, uint64_t* statsOut, unsigned statsCount)
+{
+    if (!decoder || BD(decoder)->core.ge_pending() || !statsOut || statsCount <= 0)
+        return Siamese_InvalidInput;
+    return BD(decoder)->core.stats(statsOut, statsCount);
+}
+
+SIAMESE_EXPORT unsigned sgpu_frame_write_ack(unsigned flow, const void* msg, unsigned bytes, void* out,
+                                             unsigned capacity)
+{
+    static_assert(SGPU_FRAME_ACK == kFrameAck, "SGPU_FRAME_ACK");
+    return frame_write_ack(flow, static_cast<const uint8_t*>(msg), bytes, static_cast<uint8_t*>(out), capacity);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_decoders_ack_frames(const SgpuDecoder* decoders, unsigned count,
+                                                      const unsigned* flows, unsigned byteLimit, void* deviceDst,
+                                                      size_t stride, unsigned* deviceLens, SiameseResult* results,
+                                                      unsigned* queuedOut)
+{
+    if (queuedOut)
+        *queuedOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, lens = (uint64_t)(uintptr_t)deviceLens;
+    // (a message has byteLimit bytes at most: a frame of that many must fit the row)
+    if (((!decoders || !flows) && count) || !frame_rows_ok(count, dst, stride, lens) ||
+        byteLimit < SIAMESE_ACK_MIN_BYTES || byteLimit > kFrameMaxLength - kFrameAckInner ||
+        (uint64_t)frame_header_bytes(kFrameAck, byteLimit) + byteLimit > stride)
+        return Siamese_InvalidInput;
+    for (unsigned k = 0; k < count; ++k)
+        if (!decoders[k] || BD(decoders[k])->core.ge_pending() || flows[k] > kFrameMaxFlow)
+            return Siamese_InvalidInput;
+    std::vector<uint8_t> msg(byteLimit);
+    const uint8_t none[kFrameMaxHeader] = {};
+    unsigned queued = 0;
+    SiameseResult status = Siamese_Success;
+    for (unsigned k = 0; k < count; ++k) {
+        DecoderCore& core = BD(decoders[k])->core;
+        unsigned used = 0;
+        SiameseResult r = core.acknowledgement(msg.data(), byteLimit, used);
+        if (r == Siamese_Success && (used < 1 || used > byteLimit))
+            r = Siamese_Disabled;   // (no acknowledgement is empty or longer than its limit)
+        const uint64_t row = dst + (uint64_t)k * stride, len = lens + (uint64_t)k * 4;
+        if (r == Siamese_Success) {
+            uint8_t hdr[kFrameMaxHeader] = {};
+            const unsigned h = frame_write_ack_header(flows[k], used, hdr);
+            core.program().frame_literal(msg.data(), used, hdr, h, row, len, (uint64_t)stride);
+            ++queued;
+        } else {
+            // nothing to send (nothing received yet: NeedMoreData): a zero length, the row untouched
+            core.program().frame(0, 0, none, 0, row, len, (uint64_t)stride);
+            if (r != Siamese_NeedMoreData && status == Siamese_Success)
+                status = r;
+        }
+        if (results)
+            results[k] = r;
+    }
+    Engine::global()->count_ack_frames(queued);
+    if (queuedOut)
+        *queuedOut = queued;
+    return status;
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_encoder_retransmit_frames(SgpuEncoder encoder, unsigned flow, unsigned maxPackets,
+                                                            void* deviceDst, size_t stride, unsigned maxRows,
+                                                            unsigned* deviceLens, unsigned* packetNumsOut,
+                                                            unsigned* rowsOut, unsigned* framesOut)
+{
+    if (rowsOut)
+        *rowsOut = 0;
+    if (framesOut)
+        *framesOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, lens = (uint64_t)(uintptr_t)deviceLens;
+    if (!encoder || !rowsOut || !framesOut || !frame_rows_ok(maxRows, dst, stride, lens) || flow > kFrameMaxFlow)
+        return Siamese_InvalidInput;
+    return BE(encoder)->core.retransmit_frames(flow, maxPackets, dst, (uint64_t)stride, maxRows, lens, packetNumsOut,
+                                               rowsOut, framesOut);
+}
+
+namespace {
+static_assert(SGPU_ROW_TRUNCATED == kRowTruncated && SGPU_PACKED_ACKS_DROPPED == kPackedAcksDropped,
+              "duplex scan values");
+
+inline bool duplex_ok(unsigned maxFrames, unsigned ackSlots, unsigned ackBytes)
+{
+    return maxFrames >= 1 && maxFrames <= kPackedMaxFrames && ackSlots >= 1 && ackSlots <= maxFrames &&
+           ackBytes >= kAckSlotBytesMin && ackBytes <= kAckSlotBytesMax && (ackBytes & 15u) == 0;
+}
+} // namespace
+
+SIAMESE_EXPORT size_t sgpu_frames_duplex_bytes(unsigned count, unsigned maxFrames, unsigned ackSlots,
+                                               unsigned ackBytes)
+{
+    return duplex_ok(maxFrames, ackSlots, ackBytes) ? (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes) : 0;
+}
+
+SIAMESE_EXPORT size_t sgpu_frames_duplex_slots(unsigned count, unsigned maxFrames)
+{
+    return maxFrames >= 1 && maxFrames <= kPackedMaxFrames ? (size_t)duplex_slots_offset(count, maxFrames) : 0;
+}
+
+SIAMESE_EXPORT long long sgpu_frames_scan_duplex(const void* deviceRows, size_t stride, const unsigned* deviceLens,
+                                                 unsigned count, unsigned maxFrames, unsigned ackSlots,
+                                                 unsigned ackBytes, void* pinnedOut)
+{
+    if (!g_batchReady || !rows_ok(deviceRows, stride, count) || ((uintptr_t)deviceLens & 3) ||
+        ((uintptr_t)pinnedOut & 15) || (!pinnedOut && count > 0) || !duplex_ok(maxFrames, ackSlots, ackBytes) ||
+        duplex_bytes(count, maxFrames, ackSlots, ackBytes) > ((uint64_t)1 << 32))
+        return -1;
+    return (long long)Engine::global()->duplex_rows_async(deviceRows, stride, deviceLens, count, maxFrames, ackSlots,
+                                                          ackBytes, pinnedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                     const SgpuEncoder* encoders, unsigned encoderCount,
+                                                     const void* heads, unsigned maxFrames, unsigned ackSlots,
+                                                     unsigned ackBytes, const void* deviceRows, size_t stride,
+                                                     unsigned count, SiameseResult* results,
+                                                     unsigned* nextExpectedOut, unsigned* acceptedOut)
+{
+    if (!acceptedOut)
+        return Siamese_InvalidInput;
+    *acceptedOut = 0;
+    if (!rows_ok(deviceRows, stride, count) || (!heads && count > 0) || (!decoders && decoderCount) ||
+        (!encoders && encoderCount) || ((uintptr_t)heads & 3) || !duplex_ok(maxFrames, ackSlots, ackBytes))
+        return Siamese_InvalidInput;
+    const uint64_t dev = (uint64_t)(uintptr_t)deviceRows;
+    const uint8_t* recs = static_cast<const uint8_t*>(heads);
+    const uint8_t* words = recs + (size_t)count * maxFrames * sizeof(PackedHead);
+    const uint8_t* slots = recs + (size_t)duplex_slots_offset(count, maxFrames);
+    unsigned accepted = 0;
+    SiameseResult status = Siamese_Success;
+    for (unsigned k = 0; k < count; ++k) {
+        // (the words, records and slots are the caller's memory: each is copied, checked and only then used)
+        uint32_t word;
+        std::memcpy(&word, words + (size_t)k * 4, 4);
+        SiameseResult* res = results ? results + (size_t)k * maxFrames : nullptr;
+        for (unsigned j = 0; res && j < maxFrames; ++j)
+            res[j] = Siamese_NeedMoreData;
+        unsigned n = word & kPackedCountMask;
+        bool malformed = (word & kPackedMalformed) != 0;
+        if (n > maxFrames) {   // (no scan writes such a word: none of the row's records is used)
+            n = 0;
+            malformed = true;
+        }
+        unsigned acks = 0;   // ack records met in this row
+        for (unsigned j = 0; j < n; ++j) {
+            PackedHead h;
+            std::memcpy(&h, recs + ((size_t)k * maxFrames + j) * sizeof(h), sizeof(h));
+            SiameseResult r = Siamese_InvalidInput;
+            if (h.type == kFrameAck) {
+                // a truncated message is never handed on: cut short it states another loss list
+                SgpuEncoder e = h.flow < encoderCount ? encoders[h.flow] : nullptr;
+                if (ack_head_valid(h, stride, ackSlots, ackBytes, acks) && h.status == kRowOk && e) {
+                    uint8_t msg[kAckSlotBytesMax];
+                    std::memcpy(msg, slots + ((size_t)k * ackSlots + h.packetNum) * ackBytes, h.dataBytes);
+                    unsigned next = 0;
+                    r = BE(e)->core.acknowledge(msg, h.dataBytes, next);
+                    if (nextExpectedOut)
+                        nextExpectedOut[(size_t)k * maxFrames + j] = next;
+                    ++accepted;
+                }
+                ++acks;
+            } else if (packed_head_valid(h, stride))
+                r = route_head(decoders, decoderCount, h, dev + (uint64_t)k * stride + h.offset + h.headerBytes,
+                               &accepted);
+            if (res)
+                res[j] = r;
+            if (r != Siamese_Success && r != Siamese_NeedMoreData && status == Siamese_Success)
+                status = r;
+        }
+        if (malformed) {   // the frame the walk stopped at: the slot after the row's last record, if there is one
+            if (res && n < maxFrames)
+                res[n] = Siamese_InvalidInput;
+            if (status == Siamese_Success)
+                status = Siamese_InvalidInput;
+        }
+    }
+    *acceptedOut = accepted;
+    return status;
+}
+
 SIAMESE_EXPORT long long sgpu_frames_send(unsigned count, const SgpuRecoveryPacket* packets, const unsigned* flows,
                                           void* pinnedOut, size_t capacity, size_t* bytesOut)
 {
@@ -910,14 +1122,15 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[27] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[29] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
                             s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide,
                             s.delivers,   s.frames,      s.scans,      Engine::global()->walks(),
-                            s.relays,     Engine::global()->packs()};
-    for (unsigned k = 0; k < count && k < 27; ++k)
+                            s.relays,     Engine::global()->packs(),
+                            Engine::global()->duplexes(), Engine::global()->ack_frames()};
+    for (unsigned k = 0; k < count && k < 29; ++k)
         out[k] = v[k];
 }
 

@@ -536,6 +536,85 @@ SiameseResult EncoderCore::pack_frames(unsigned flow, unsigned firstNum, unsigne
     return Siamese_Success;
 }
 
+SiameseResult EncoderCore::retransmit_frames(unsigned flow, unsigned maxPackets, uint64_t dst, uint64_t stride,
+                                             unsigned maxRows, uint64_t lens, unsigned* packetNums, unsigned* rows,
+                                             unsigned* frames)
+{
+    *rows = *frames = 0;
+    if (dead())
+        return Siamese_Disabled;
+    // the longest frame a retransmission of the current window can need
+    uint64_t worst = 0;
+    for (unsigned e = firstUnremoved_; e < count_; ++e) {
+        const EncSlot& s = slot(e);
+        if (s.bytes > s.header) {
+            const unsigned n = s.bytes - s.header;
+            worst = std::max<uint64_t>(worst, (uint64_t)frame_header_bytes(kFrameOriginal, n) + n);
+        }
+    }
+    if (worst > stride)
+        return Siamese_InvalidInput;
+    struct Sent
+    {
+        uint64_t src;
+        uint32_t bytes, column;
+        uint8_t prefix[kMaxLengthPrefix];   // the symbol prefix pack_plan reads the length from
+        uint32_t cap;
+    };
+    std::vector<Sent> sent;
+    uint64_t row = 0, off = 0;   // pack_frames' cursor
+    while (sent.size() < maxPackets) {
+        if ((off + worst > stride ? row + 1 : row) >= maxRows)
+            break;   // the next packet might not fit: it is not asked for
+        SiameseOriginalPacket p;
+        const SiameseResult r = retransmit(p);
+        if (r == Siamese_NeedMoreData)
+            break;
+        if (r != Siamese_Success)
+            return r;
+        Sent s;
+        s.src = (uint64_t)(uintptr_t)p.Data;
+        s.bytes = p.DataBytes;
+        s.column = p.PacketNum;
+        std::memset(s.prefix, 0, sizeof(s.prefix));
+        s.cap = write_length_prefix(p.DataBytes, s.prefix) + p.DataBytes;
+        sent.push_back(s);
+        const uint64_t T = (uint64_t)frame_header_bytes(kFrameOriginal, p.DataBytes) + p.DataBytes;
+        if (off + T > stride) {
+            ++row;
+            off = 0;
+        }
+        off = (off + T + 15) & ~(uint64_t)15;
+    }
+    const uint32_t count = (uint32_t)sent.size();
+    std::vector<const uint8_t*> syms(count);
+    std::vector<uint32_t> caps(count), rowLens(maxRows);
+    std::vector<PlanRec> recs(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        syms[k] = sent[k].prefix;
+        caps[k] = sent[k].cap;
+    }
+    uint32_t info[4];
+    pack_plan(syms.data(), caps.data(), count, stride, maxRows, recs.data(), rowLens.data(), info);
+    for (uint32_t k = 0; k < count; ++k) {   // (every packet is a frame of a row below maxRows: checked before it was taken)
+        const Sent& s = sent[k];
+        uint8_t hdr[kFrameMaxHeader] = {};
+        const unsigned h = frame_write_header(kFrameOriginal, flow, s.column, s.bytes, hdr);
+        const bool last = k + 1 == count || recs[k + 1].row != recs[k].row;
+        const uint64_t at = (uint64_t)recs[k].off16 << 4;
+        prog_.frame(s.src, s.bytes, hdr, h, dst + recs[k].row * stride + at, last ? lens + (uint64_t)recs[k].row * 4 : 0,
+                    (uint64_t)recs[k].span16 << 4, last ? (uint32_t)at : 0);
+        if (packetNums)
+            packetNums[k] = s.column;
+    }
+    const uint8_t none[kFrameMaxHeader] = {};
+    for (uint64_t r = info[0]; r < maxRows; ++r)   // rows not used: only a zero length
+        prog_.frame(0, 0, none, 0, dst + r * stride, lens + r * 4, stride);
+    *rows = info[0];
+    *frames = count;
+    return Siamese_Success;
+}
+
 // ---------------------------------------------------------------------------
 // Encode
 

@@ -145,6 +145,22 @@ public:
     SiameseResult pack_frames(unsigned flow, unsigned firstNum, unsigned originalCount, const PackRecovery* rec,
                               unsigned recCount, uint64_t dst, uint64_t stride, unsigned maxRows, uint64_t lens,
                               SiameseResult* results, unsigned* rows, unsigned* frames);
+    /// sgpu_encoder_retransmit_frames: retransmit() until it answers
+    /// NeedMoreData or maxPackets packets were returned, each queued as a
+    /// kFrameOriginal frame for `flow` into rows of `stride` bytes at dst + row *
+    /// stride, laid out by pack_frames' cursor rule (frames.h pack_plan makes the
+    /// layout from the lengths, Program::frame places it: rows written whole,
+    /// length words as pack_frames writes them, zero for rows [*rows, maxRows)).
+    /// retransmit() stamps the packet it returns, so none is asked for that
+    /// could not be placed: before each call a frame of the longest original of
+    /// the unacknowledged window must fit the rows that are left, or the call
+    /// ends with Success and what it has; when such a frame does not fit
+    /// `stride` at all, InvalidInput with nothing consumed and nothing queued.
+    /// packetNums[i] (optional) = frame i's PacketNum.  A result of retransmit()
+    /// other than Success and NeedMoreData is returned, nothing being queued.
+    SiameseResult retransmit_frames(unsigned flow, unsigned maxPackets, uint64_t dst, uint64_t stride,
+                                    unsigned maxRows, uint64_t lens, unsigned* packetNums, unsigned* rows,
+                                    unsigned* frames);
     /// Generate the next recovery packet (device ops queued, not flushed).
     SiameseResult encode(EncodeOut& out);
     /// `count` encode() calls in one (sgpu_encode_range): out[k] as the k-th

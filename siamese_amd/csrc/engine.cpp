@@ -119,6 +119,8 @@ void ProgramBody::clear()
     lcb.clear();
     ndeliver = 0;   // (the items' vector keeps its elements: not touched here)
     nframe = 0;
+    frameLit.clear();
+    frameLitRefs.clear();
     nrelay = 0;
     npackjob = npack = 0;
     gateOpen = false;
@@ -908,6 +910,17 @@ void Program::frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t h
     if (b_->nframe == b_->frames.size())
         b_->frames.emplace_back();
     b_->frames[b_->nframe++] = it;
+}
+
+void Program::frame_literal(const uint8_t* data, uint32_t bytes, const uint8_t* hdr, uint32_t hdrLen, uint64_t dst,
+                            uint64_t lenOut, uint64_t stride)
+{
+    touch();
+    const size_t at = b_->frameLit.size();
+    b_->frameLit.resize(align16(at + bytes), 0);
+    std::memcpy(b_->frameLit.data() + at, data, bytes);
+    b_->frameLitRefs.push_back(ProgramBody::FrameLitRef{b_->nframe, (uint32_t)at});
+    frame(1 /* assembly: the literal's place in the upload */, bytes, hdr, hdrLen, dst, lenOut, stride);
 }
 
 void Program::relay(uint64_t src, uint32_t cap, uint32_t flow, uint32_t packetNum, uint64_t dst, uint64_t lenOut,
@@ -2249,6 +2262,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     size_t geInBytes = 0;
     size_t nDeliver = 0;   // delivery items of every body
     size_t nFrame = 0;     // frame items of every body
+    size_t frameLitBytes = 0;   // and the bytes they carry themselves
     size_t nRelay = 0;     // relay items of every body
     size_t nPackJob = 0, nPack = 0;   // pack jobs and items of every body
     for (int g = 0; g < 2; ++g)
@@ -2256,6 +2270,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
             const ProgramBody* p = bt.bodies[g][pi];
             nDeliver += p->ndeliver;   // (beside nges: no line of the body this pass does not read anyway)
             nFrame += p->nframe;
+            frameLitBytes += p->frameLit.size();   // (each a multiple of 16)
             nRelay += p->nrelay;
             nPackJob += p->npackjob;
             nPack += p->npack;
@@ -2372,6 +2387,9 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     off = align16(off + nPackJob * sizeof(PackJob));
     bt.oPack = off;
     off = align16(off + nPack * sizeof(PackItem));
+    // the frame items' own bytes (Program::frame_literal)
+    const size_t oFrameLit = off;
+    off = align16(off + frameLitBytes);
     // the download copy list (the counters and results, then every range)
     size_t nDownloads = 0;
     for (const Shard::Queues& q : bt.queues)
@@ -2586,6 +2604,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     if (nFrame) {
         FrameItem* fi = (FrameItem*)(up + bt.oFrame);
         uint32_t max16 = 0;
+        size_t litBase = 0;
         for (int g = 0; g < 2; ++g)
             for (const ProgramBody* p : bt.bodies[g]) {
                 if (p->nframe == 0)
@@ -2593,6 +2612,12 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
                 std::memcpy(fi, p->frames.data(), p->nframe * sizeof(FrameItem));
                 for (uint32_t k = 0; k < p->nframe; ++k)
                     max16 = std::max(max16, fi[k].stride16);
+                if (!p->frameLit.empty()) {
+                    std::memcpy(up + oFrameLit + litBase, p->frameLit.data(), p->frameLit.size());
+                    for (const ProgramBody::FrameLitRef& r : p->frameLitRefs)
+                        fi[r.item].src = (uint64_t)(uintptr_t)(bt.upBase + oFrameLit + litBase) + r.offset;
+                    litBase += p->frameLit.size();
+                }
                 fi += p->nframe;
             }
         bt.maxFrameStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
@@ -3053,8 +3078,9 @@ int64_t Engine::gather_async_framed(unsigned count, const void* const* srcs, con
 }
 
 // scan_rows_async (maxFrames == 0: k_scan) and walk_rows_async (k_walk)
+// and duplex_rows_async (ackSlots != 0: k_ackwalk)
 int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
-                           unsigned maxFrames, void* pinnedOut)
+                           unsigned maxFrames, void* pinnedOut, unsigned ackSlots, unsigned ackBytes)
 {
     if (failed())
         return -1;
@@ -3066,7 +3092,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     if (!gather_land(g))   // (the slot's previous gather, kGatherSlots back)
         return -1;
     // the records take the slot's packing area; a scan uploads no descriptors
-    const size_t total = maxFrames ? (size_t)packed_bytes(count, maxFrames) : (size_t)count * sizeof(RowHead);
+    const size_t total = ackSlots    ? (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes)
+                         : maxFrames ? (size_t)packed_bytes(count, maxFrames)
+                                     : (size_t)count * sizeof(RowHead);
     if (total > g.stageCap) {
         size_t c = g.stageCap ? g.stageCap : (1u << 20);
         while (c < total)
@@ -3079,13 +3107,17 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     if (!g.stage)
         return -1;
     void* packed = nullptr;
-    if (!(maxFrames ? be_walk_rows(rows, stride, lens, count, maxFrames, g.stage, pinnedOut, &packed, &g.landed)
-                    : be_scan_rows(rows, stride, lens, count, g.stage, pinnedOut, &packed, &g.landed))) {
+    if (!(ackSlots    ? be_ackwalk_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, g.stage, pinnedOut,
+                                        &packed, &g.landed)
+          : maxFrames ? be_walk_rows(rows, stride, lens, count, maxFrames, g.stage, pinnedOut, &packed, &g.landed)
+                      : be_scan_rows(rows, stride, lens, count, g.stage, pinnedOut, &packed, &g.landed))) {
         failed_.store(true, std::memory_order_relaxed);
         return -1;
     }
     g.ticket = ticket;
-    if (maxFrames)
+    if (ackSlots)
+        duplexes_.fetch_add(count, std::memory_order_relaxed);
+    else if (maxFrames)
         walks_.fetch_add(count, std::memory_order_relaxed);
     else {
         std::lock_guard<std::mutex> s(statsMu_);

@@ -354,6 +354,17 @@ struct ProgramBody
     /// FrameItem), run by the submission's one k_frame launch beside
     /// k_deliver's.  nframe in use (capacity is kept).
     std::vector<FrameItem> frames;
+    /// Bytes that frame items carry themselves (Program::frame_literal: an
+    /// acknowledgement message made on the host): they ride in the
+    /// submission's upload, and assembly points each listed item's src at its
+    /// bytes there.  Every literal starts on a 16-byte boundary of frameLit.
+    struct FrameLitRef
+    {
+        uint32_t item;     // index into frames
+        uint32_t offset;   // of the literal in frameLit
+    };
+    std::vector<uint8_t> frameLit;
+    std::vector<FrameLitRef> frameLitRefs;
     /// A decoder's packets to forward as wire frames into the caller's device
     /// rows (ops.h RelayItem), run by the submission's one k_relay launch
     /// beside k_deliver's.  nrelay in use (capacity is kept).
@@ -547,6 +558,11 @@ public:
     /// only work is framing still makes a submission.
     void frame(uint64_t src, uint32_t bytes, const uint8_t* hdr, uint32_t hdrLen, uint64_t dst, uint64_t lenOut,
                uint64_t stride, uint32_t lenBase = 0);
+    /// frame() whose packet is data[0, bytes) (bytes >= 1), host memory that is
+    /// copied here: the bytes cross in the submission's upload, from where
+    /// k_frame places them like any other source.
+    void frame_literal(const uint8_t* data, uint32_t bytes, const uint8_t* hdr, uint32_t hdrLen, uint64_t dst,
+                       uint64_t lenOut, uint64_t stride);
 
     /// Queue a relay item (ops.h RelayItem): deliver()'s arguments, and the
     /// flow and PacketNum of the original's frame the device writes in front of
@@ -727,6 +743,15 @@ public:
     {
         return rows_async(rows, stride, lens, count, maxFrames, pinnedOut);
     }
+    /// The same for the rows of a bidirectional flow: the packed scan's output
+    /// and then ackSlots (>= 1) message slots of ackBytes bytes per row,
+    /// duplex_bytes(count, maxFrames, ackSlots, ackBytes) in all, into pinnedOut
+    /// (k_ackwalk, sgpu_frames_scan_duplex).
+    int64_t duplex_rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
+                              unsigned maxFrames, unsigned ackSlots, unsigned ackBytes, void* pinnedOut)
+    {
+        return rows_async(rows, stride, lens, count, maxFrames, pinnedOut, ackSlots, ackBytes);
+    }
     /// Wait until gather `ticket` and every earlier one have landed.
     bool gather_wait(int64_t ticket);
     /// Host -> device copy on the staging stream, issued now; every later
@@ -900,17 +925,24 @@ private:
     int64_t gNext_ = 0;
     bool gather_land(GatherSlot& g);
     int64_t rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count, unsigned maxFrames,
-                       void* pinnedOut);
+                       void* pinnedOut, unsigned ackSlots = 0, unsigned ackBytes = 0);
     // rows scanned by the packed scan, counted when the scan is queued (sgpu_engine_stats_ex [24]); kept
     // here, behind every other member, and not in EngineStats, whose size every submission's counters share
     std::atomic<uint64_t> walks_{0};
     // pack items queued (sgpu_decoder_pack_frames), counted when their submission is launched
     // (sgpu_engine_stats_ex [26]); here for the same reason
     std::atomic<uint64_t> packs_{0};
+    // rows scanned by the duplex scan, counted as walks_ ([27]), and ack frames queued
+    // (sgpu_decoders_ack_frames), counted by the call ([28]); here for the same reason
+    std::atomic<uint64_t> duplexes_{0};
+    std::atomic<uint64_t> ackFrames_{0};
 
 public:
     uint64_t walks() const { return walks_.load(std::memory_order_relaxed); }
     uint64_t packs() const { return packs_.load(std::memory_order_relaxed); }
+    uint64_t duplexes() const { return duplexes_.load(std::memory_order_relaxed); }
+    uint64_t ack_frames() const { return ackFrames_.load(std::memory_order_relaxed); }
+    void count_ack_frames(uint64_t n) { ackFrames_.fetch_add(n, std::memory_order_relaxed); }
 };
 
 /// Per-host-thread engine state.  Only its owning thread touches it between

@@ -4,11 +4,16 @@
 // A frame carries one datagram:
 //   [L: length of the rest, the symbol length prefix format
 //       (reference SiameseSerializers.h:566-593), 1-4 bytes]
-//   [type: 1 byte]  kFrameOriginal / kFrameRecovery
+//   [type: 1 byte]  kFrameOriginal / kFrameRecovery / kFrameAck
 //   [flow: 3 bytes little-endian]  the application's stream id
 //   original:  [PacketNum: 3 bytes LE (22 bits)] [payload]
 //   recovery:  [the recovery packet: payload + its metadata footer
 //               (reference SiameseSerializers.h:736-800)]
+//   ack:       [the acknowledgement message, exactly as the decoder wrote it
+//               (reference SiameseDecoder.cpp:125-255): at least one byte, so
+//               L >= 5, and no upper bound but the frame format's]
+// Only the duplex scan (ack_walk below) accepts an ack frame; frames_parse,
+// row_head_scan and row_walk call type 2 malformed.
 // Frames follow each other directly; a zero byte where a frame would start
 // is an empty frame (L = 0) and is skipped, so senders may pad frames to
 // any alignment with zeros (the egress gather places each frame at a 16-byte
@@ -27,11 +32,13 @@ namespace sgpu {
 
 constexpr uint8_t kFrameOriginal = 0;
 constexpr uint8_t kFrameRecovery = 1;
+constexpr uint8_t kFrameAck = 2;
 constexpr unsigned kFrameFlowBytes = 3;
 constexpr unsigned kFrameMaxFlow = (1u << 24) - 1;
 /// Bytes between a frame's length prefix and its data.
 constexpr unsigned kFrameOriginalInner = 1 + kFrameFlowBytes + 3;   // type, flow, PacketNum
 constexpr unsigned kFrameRecoveryInner = 1 + kFrameFlowBytes;       // type, flow
+constexpr unsigned kFrameAckInner = 1 + kFrameFlowBytes;            // type, flow
 
 /// One parsed frame: byte offsets into the buffer it was parsed from.
 struct FrameInfo
@@ -67,6 +74,30 @@ inline unsigned frame_write_header(unsigned type, unsigned flow, unsigned packet
         out[n++] = (uint8_t)(packetNum >> 16);
     }
     return n;
+}
+/// The header of an ack frame for `flow` whose message has `bytes` bytes (1 ..
+/// kFrameMaxLength - 4), at most 8 bytes: returns its size.
+inline unsigned frame_write_ack_header(unsigned flow, unsigned bytes, uint8_t* out)
+{
+    unsigned n = write_length_prefix(kFrameAckInner + bytes, out);
+    out[n++] = kFrameAck;
+    out[n++] = (uint8_t)flow;
+    out[n++] = (uint8_t)(flow >> 8);
+    out[n++] = (uint8_t)(flow >> 16);
+    return n;
+}
+/// An ack frame for `flow` around msg[0, bytes) into out[0, capacity): returns
+/// the frame's bytes, 0 when there is no message, the flow has more than three
+/// bytes, L cannot be stated or the frame does not fit.
+inline unsigned frame_write_ack(unsigned flow, const uint8_t* msg, unsigned bytes, uint8_t* out, size_t capacity)
+{
+    if (!msg || !out || bytes < 1 || flow > kFrameMaxFlow || bytes > kFrameMaxLength - kFrameAckInner)
+        return 0;
+    if ((uint64_t)frame_header_bytes(kFrameAck, bytes) + bytes > capacity)
+        return 0;
+    const unsigned n = frame_write_ack_header(flow, bytes, out);
+    std::memcpy(out + n, msg, bytes);
+    return n + bytes;
 }
 /// No malformed frame was met (frames_parse's *badOffset).
 constexpr size_t kNoBadFrame = ~(size_t)0;
@@ -225,6 +256,105 @@ inline uint32_t row_walk(const uint8_t* row, uint64_t stride, const uint32_t* le
         at += (uint64_t)h + length;
     }
     return n;
+}
+
+/// Rows of a bidirectional flow (ops.h kRowTruncated, sgpu_frames_scan_duplex /
+/// sgpu_frames_recv_duplex).  The one definition of an ack record that a duplex
+/// scan with these ackSlots and ackBytes can have produced for a row of
+/// `stride` bytes: type kFrameAck; at least one message byte; a header of the
+/// four inner bytes plus a 1-4 byte prefix; the frame within the stride; a flow
+/// of three bytes; no tail and no head; packetNum = nth, the ack records before
+/// it in its row; status kRowOk with a slot (packetNum < ackSlots) that holds
+/// the whole message (dataBytes <= ackBytes), or kRowTruncated with one of the
+/// two failing.  sgpu_frames_recv_duplex trusts no ack record that fails it,
+/// and hands only the kRowOk ones to an encoder.
+inline bool ack_head_valid(const PackedHead& r, uint64_t stride, uint32_t ackSlots, uint32_t ackBytes, uint32_t nth)
+{
+    if (r.type != kFrameAck || r.packetNum != nth || (r.status != kRowOk && r.status != kRowTruncated))
+        return false;
+    if (r.dataBytes < 1 || r.dataBytes > kFrameMaxLength - kFrameAckInner)
+        return false;
+    if (r.headerBytes < kFrameAckInner + 1 || r.headerBytes > kFrameAckInner + 4 || r.tailBytes != 0)
+        return false;
+    if ((uint64_t)r.offset + r.headerBytes + r.dataBytes > stride || r.flow > kFrameMaxFlow)
+        return false;
+    for (unsigned i = 0; i < 4; ++i)
+        if (r.head[i] | r.tail[i] | r.tail[4 + i])
+            return false;
+    const bool whole = r.packetNum < ackSlots && r.dataBytes <= ackBytes;
+    return whole == (r.status == kRowOk);
+}
+
+/// What k_ackwalk computes for one row: row_walk's arguments, and slots = the
+/// row's ackSlots message slots of ackBytes bytes each.  The walk is row_walk's
+/// with one more type: a frame of type kFrameAck with L > 4 is accepted, as the
+/// row's a-th ack (a counts from 0).  Its record is what ack_head_valid
+/// describes, with packetNum = a and dataBytes = D = L - 4; slot a, when a <
+/// ackSlots, gets the message's first min(D, ackBytes) bytes.  An ack without a
+/// slot, or longer than its slot, has status kRowTruncated and sets
+/// kPackedAcksDropped in the row word; the walk goes on behind it.  Originals
+/// and recovery frames give row_walk's records.  Every record and every slot
+/// byte is written: records past the last frame and slot bytes past a message
+/// are zero.  Returns the row word.
+inline uint32_t ack_walk(const uint8_t* row, uint64_t stride, const uint32_t* len, uint32_t maxFrames,
+                         uint32_t ackSlots, uint32_t ackBytes, PackedHead* out, uint8_t* slots)
+{
+    std::memset(out, 0, (size_t)maxFrames * sizeof(*out));
+    std::memset(slots, 0, (size_t)ackSlots * ackBytes);
+    const uint64_t end = len ? *len : stride;
+    if (end > stride)
+        return kPackedMalformed;
+    uint64_t at = 0;
+    uint32_t n = 0, acks = 0, flags = 0;
+    while (at < end) {
+        if (row[at] == 0) {
+            ++at;
+            continue;
+        }
+        if (n == maxFrames)
+            return n | flags | kPackedMore;
+        const uint64_t left = end - at;
+        unsigned length = 0;
+        const int h = read_length_prefix(row + at, left < 4 ? (unsigned)left : 4u, &length);
+        if (h < 1 || length < 1 || (uint64_t)h + length > left)
+            return n | flags | kPackedMalformed;
+        const uint8_t* f = row + at + h;   // type, flow, PacketNum: before end when L > inner
+        PackedHead r;
+        std::memset(&r, 0, sizeof(r));
+        r.offset = (uint32_t)at;
+        r.status = kRowOk;
+        r.type = f[0];
+        const unsigned inner = r.type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+        if (r.type > kFrameAck || length <= inner)
+            return n | flags | kPackedMalformed;
+        r.headerBytes = (uint8_t)(h + inner);
+        r.flow = f[1] | ((uint32_t)f[2] << 8) | ((uint32_t)f[3] << 16);
+        r.dataBytes = length - inner;
+        if (r.type == kFrameAck) {
+            r.packetNum = acks;
+            if (acks < ackSlots)
+                std::memcpy(slots + (size_t)acks * ackBytes, row + at + r.headerBytes,
+                            r.dataBytes < ackBytes ? r.dataBytes : ackBytes);
+            if (acks >= ackSlots || r.dataBytes > ackBytes) {
+                r.status = kRowTruncated;
+                flags |= kPackedAcksDropped;
+            }
+            ++acks;
+        } else {
+            r.packetNum = r.type == kFrameOriginal ? f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) : 0;
+            r.tailBytes = r.type == kFrameRecovery ? (uint8_t)(r.dataBytes < 8 ? r.dataBytes : 8) : 0;
+            if (!packed_head_valid(r, end))
+                return n | flags | kPackedMalformed;
+            if (r.type == kFrameRecovery) {
+                const uint8_t* data = row + at + r.headerBytes;
+                std::memcpy(r.head, data, r.dataBytes < 4 ? r.dataBytes : 4);
+                std::memcpy(r.tail + 8 - r.tailBytes, data + r.dataBytes - r.tailBytes, r.tailBytes);
+            }
+        }
+        out[n++] = r;
+        at += (uint64_t)h + length;
+    }
+    return n | flags;
 }
 
 /// What k_relay computes for one present item (ops.h RelayItem): the symbol

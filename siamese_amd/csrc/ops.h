@@ -592,6 +592,32 @@ constexpr uint64_t packed_bytes(uint64_t count, uint64_t maxFrames)
     return count * maxFrames * sizeof(PackedHead) + count * 4;
 }
 
+/// Rows of a bidirectional flow (k_ackwalk, sgpu_frames_scan_duplex): k_walk's
+/// records and row words, with acknowledgement frames (frames.h kFrameAck)
+/// accepted, and behind the row words, from the next 16-byte boundary on,
+/// ackSlots message slots of ackBytes bytes per row (row k's at slot index
+/// k * ackSlots).  The row's a-th ack frame, of D message bytes, gets a record
+/// with type kFrameAck, packetNum = a, dataBytes = D, no head and no tail; when
+/// a < ackSlots, slot a holds the message's first min(D, ackBytes) bytes and
+/// zeros after them.  Its status is kRowOk when a < ackSlots and D <= ackBytes,
+/// otherwise kRowTruncated, and the row word then carries kPackedAcksDropped:
+/// the walk goes on either way.  Slots without an ack are zero (frames.h
+/// ack_walk states the walk).
+constexpr uint8_t kRowTruncated = 3;
+constexpr uint32_t kPackedAcksDropped = 0x20000000u;
+constexpr uint32_t kAckSlotBytesMin = 16, kAckSlotBytesMax = 1024;   // ackBytes: a multiple of 16 between them
+/// k_ackwalk: one lane per row, kAckWalkThreads rows per workgroup.
+constexpr uint32_t kAckWalkThreads = 256;
+/// Where a duplex scan's slots start, and its output's bytes.
+constexpr uint64_t duplex_slots_offset(uint64_t count, uint64_t maxFrames)
+{
+    return (packed_bytes(count, maxFrames) + 15) & ~(uint64_t)15;
+}
+constexpr uint64_t duplex_bytes(uint64_t count, uint64_t maxFrames, uint64_t ackSlots, uint64_t ackBytes)
+{
+    return duplex_slots_offset(count, maxFrames) + count * ackSlots * ackBytes;
+}
+
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)
 /// Solves with more rows than this stage 256-byte tiles (16 lanes x 16 bytes

@@ -1,0 +1,28 @@
+"""frames.h ack_walk and ack_head_valid alone (tests/ack_walk_test.cpp): the
+plain C++ statement of one k_ackwalk row and the record check
+sgpu_frames_recv_duplex makes, built as a stand-alone host program with
+-fsanitize=address,undefined and run on the CPU.  Every row, record array and
+slot array of the program ends where its heap block ends, so the sanitizer
+checks the bytes ack_walk may read and write; the program checks the records,
+the row words and the slots themselves."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_ack_walk_under_sanitizers(tmp_path):
+    exe = str(tmp_path / "ack_walk_test")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g"] + san + ["-static-libasan", "-static-libubsan",
+                   "-I", os.path.join(ROOT, "siamese_amd", "csrc"), os.path.join(ROOT, "tests", "ack_walk_test.cpp"),
+                   "-o", exe], check=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
+    assert "ack_walk ok" in out.stdout

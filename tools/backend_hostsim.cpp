@@ -719,6 +719,27 @@ bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint3
     return true;
 }
 
+// k_ackwalk (ops.h kRowTruncated): frames.h ack_walk per row, the row words
+// after the records and the slots from the next 16-byte boundary on.
+bool be_ackwalk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                     uint32_t ackSlots, uint32_t ackBytes, void* devStage, void* hostOut, void** packed,
+                     void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    PackedHead* out = static_cast<PackedHead*>(devStage);
+    uint8_t* words = static_cast<uint8_t*>(devStage) + (size_t)count * maxFrames * sizeof(PackedHead);
+    uint8_t* slots = static_cast<uint8_t*>(devStage) + (size_t)duplex_slots_offset(count, maxFrames);
+    std::memset(words + (size_t)count * 4, 0, (size_t)(slots - (words + (size_t)count * 4)));
+    for (uint32_t k = 0; k < count; ++k) {
+        const uint32_t w = ack_walk(static_cast<const uint8_t*>(rows) + (uint64_t)k * stride, stride,
+                                    lens ? lens + k : nullptr, maxFrames, ackSlots, ackBytes,
+                                    out + (size_t)k * maxFrames, slots + (size_t)k * ackSlots * ackBytes);
+        std::memcpy(words + (size_t)k * 4, &w, 4);
+    }
+    std::memcpy(hostOut, devStage, (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes));
+    return true;
+}
+
 // HOSTSIM_FAIL_SYNC=N: the N-th be_sync (1-based) and every later one
 // report a device fault (tests of the sticky Disabled path).
 bool be_sync()

@@ -144,6 +144,15 @@ bool be_walk_rows(const void*, uint64_t, const uint32_t*, uint32_t count, uint32
     return true;
 }
 
+bool be_ackwalk_rows(const void*, uint64_t, const uint32_t*, uint32_t count, uint32_t maxFrames, uint32_t ackSlots,
+                     uint32_t ackBytes, void* devStage, void* hostOut, void** packed, void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    std::memset(devStage, 0, (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes));
+    std::memcpy(hostOut, devStage, (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes));
+    return true;
+}
+
 bool be_sync() { return true; }
 void* be_fence() { return reinterpret_cast<void*>(1); }
 bool be_fence_wait(void*, unsigned, bool) { return true; }
