@@ -722,6 +722,57 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_pack_frames(SgpuDecoder decoder, unsig
                                                       unsigned* deviceInfo /* 4 x uint32, device, 16-byte aligned */,
                                                       SiameseResult* results /* host, count, optional */,
                                                       unsigned* queuedOut);
+/// The last leg of the receive path: the packets firstPacketNum ..
+/// firstPacketNum+count-1 of `decoder` as the in-order byte stream the
+/// application is owed, payloads back to back in deviceDst[0, capacity) with no
+/// holes, no padding and no framing -- what sgpu_encoder_add_range(stride =
+/// fixedBytes) segmented at the sender, reassembled.  deviceDst may have any
+/// byte alignment: a receiver appends at its write cursor, buf + bytesSoFar.
+/// The offsets are summed on the device, from the lengths it reads there, so a
+/// packet whose solve is queued in this same submission (sgpu_decode,
+/// sgpu_decode_device) is delivered without a wait.
+///
+/// Host side.  p = the leading present packets of the range, presence as in
+/// sgpu_decoder_deliver_range (a packet whose solve is queued in this
+/// submission counts).  results[k] = Siamese_Success for k < p and
+/// Siamese_NeedMoreData for k >= p: the stream cannot reach a packet behind a
+/// hole, whose length is unknown.  *queuedOut = p.
+///
+/// Device side.  Packet k < p has payload length n_k, valid as
+/// sgpu_decoder_deliver_range judges it (a readable prefix, n >= 1, within the
+/// symbol's capacity).  With off_0 = 0, packet k is delivered when every packet
+/// before it was, it is valid and off_k + n_k <= capacity; then
+/// deviceDst[off_k, off_k + n_k) is its payload and off_{k+1} = off_k + n_k.
+/// Whole packets only.  With d packets delivered and B = off_d:
+/// deviceOffsets[k] = off_k for k <= d and B for d < k <= count, so
+/// deviceOffsets[k+1] - deviceOffsets[k] is always the delivered length of
+/// packet k; deviceInfo = {d, B, stop, p} with stop 0 when d == p, 1 when
+/// packet d is invalid (a corrupt recovered prefix: the decoder reports it as
+/// it always does) and 2 when it is valid but does not fit capacity.  No byte
+/// of deviceDst outside [0, B) is written, below deviceDst and at or past
+/// deviceDst + B included: a word shared with bytes the caller already holds is
+/// never read and rewritten.  Never waits; everything is in place when the
+/// carrying submission completes; the launch runs after every other launch of
+/// its submission; the lifetime and overlap rules are
+/// sgpu_decoder_deliver_range's, deviceOffsets and deviceInfo included.
+///
+/// Siamese_InvalidInput, with nothing queued: a null decoder, queuedOut,
+/// deviceOffsets or deviceInfo; deviceOffsets not 4-byte aligned; deviceInfo
+/// not 16-byte aligned; null deviceDst with capacity > 0; capacity > 2^32 - 1;
+/// count > 65535; firstPacketNum > SIAMESE_PACKET_NUM_MAX; a decoder with a
+/// device matrix job pending.  A dead decoder returns Siamese_Disabled.
+/// count == 0 returns Siamese_Success, writes deviceOffsets[0] = 0 and a zero
+/// deviceInfo and copies nothing.  Lengths known on the host are not checked
+/// against capacity: a full buffer is an ordinary stop (2), not an error, and
+/// the next call appends from packet firstPacketNum + d.  Delivery past a hole,
+/// framing inside the stream, a counterpart on the encoder or in the drop-in
+/// ABI, and a capacity of 4 GiB or more are not offered.
+SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_stream(SgpuDecoder decoder, unsigned firstPacketNum, unsigned count,
+                                                         void* deviceDst, size_t capacity,
+                                                         unsigned* deviceOffsets /* count + 1 uint32, device */,
+                                                         unsigned* deviceInfo /* 4 x uint32, device, 16-byte aligned */,
+                                                         SiameseResult* results /* host, count, optional */,
+                                                         unsigned* queuedOut);
 
 /*
     Closing the loop: the ARQ half of the codec for batch instances.  The
@@ -891,7 +942,8 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// gather has been waited for), [8] k_walk (sgpu_frames_scan_packed,
 /// likewise), [9] k_relay (sgpu_decoder_deliver_frames), [10] k_plan and [11]
 /// k_pack (sgpu_decoder_pack_frames), [12] k_ackwalk (sgpu_frames_scan_duplex,
-/// counted as k_walk is); count entries at most.
+/// counted as k_walk is), [13] k_offsets and [14] k_concat
+/// (sgpu_decoder_deliver_stream); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -917,7 +969,9 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// [26] the pack items queued (sgpu_decoder_pack_frames: one per packet of the
 /// range, absent ones included), then [27] the rows scanned by
 /// sgpu_frames_scan_duplex, counted as [24], then [28] the ack frames queued
-/// (sgpu_decoders_ack_frames, counted by the call); count entries at most.
+/// (sgpu_decoders_ack_frames, counted by the call), then [29] the stream items
+/// queued (sgpu_decoder_deliver_stream: one per packet of the range's leading
+/// present run, counted as [26]); count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

@@ -112,6 +112,16 @@ def bind_duplex_abi(L):
     return L
 
 
+def bind_stream_abi(L):
+    """Prototype of sgpu_decoder_deliver_stream: a decoder's packets as one
+    contiguous byte stream at any byte alignment, summed and copied on the
+    device."""
+    vp, u, sz = ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t
+    L.sgpu_decoder_deliver_stream.restype = ctypes.c_int
+    L.sgpu_decoder_deliver_stream.argtypes = [vp, u, u, vp, sz, vp, vp, vp, vp]
+    return L
+
+
 class SiameseError(RuntimeError):
     def __init__(self, what, code):
         name = RESULT_NAMES[code] if 0 <= code < 6 else str(code)

@@ -162,6 +162,15 @@ void be_launch_relay(const RelayItem* items, uint32_t count, uint32_t maxStride)
 /// saturated at 2^32 - 1 (k_pack's grid).  Queued beside be_launch_deliver.
 void be_launch_pack(const PackJob* jobs, uint32_t jobCount, const PackItem* items, uint32_t count, PlanRec* plan,
                     uint32_t maxStride);
+/// A decoder's packets as one contiguous byte stream (ops.h ConcatJob,
+/// ConcatItem, ConcatRec): k_offsets sums every job's lengths, read on the
+/// device, into recs[0, count) and writes the jobs' offset words and info
+/// records; k_concat then copies every delivered payload to its byte offset.
+/// recs is device memory of the submission, count records, which the host
+/// never reads; maxBytes is the longest symbol in bytes (k_concat's grid).
+/// Queued beside be_launch_deliver.
+void be_launch_concat(const ConcatJob* jobs, uint32_t jobCount, const ConcatItem* items, uint32_t count,
+                      ConcatRec* recs, uint32_t maxBytes);
 
 /// Block until all queued work has finished.  Returns false on a device fault.
 bool be_sync();
@@ -240,6 +249,8 @@ enum BeKernel
     kBePlan,
     kBePack,
     kBeAckWalk,
+    kBeOffsets,
+    kBeConcat,
     kBeKernelKinds
 };
 void be_timing_enable(bool on);

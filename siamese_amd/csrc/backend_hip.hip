@@ -23,6 +23,8 @@
 //                  header computed from the length read on the device
 //   k_plan, k_pack the same frames several to a row: the packer's layout made
 //                  on the device from those lengths, then k_relay's copy
+//   k_offsets, k_concat  decoded packets as one contiguous byte stream: a prefix
+//                  sum over those lengths, then a copy to byte-granular offsets
 //   k_frame        a sender's originals and recovery packets as wire frames
 //                  into caller-owned rows (header, packet, zero tail; opt-in)
 //   k_scan         frame rows in device memory into 32-byte host records
@@ -4249,6 +4251,215 @@ __global__ __launch_bounds__(64 * kDeliverWaves) void k_pack(const PackJob* __re
 }
 
 // ---------------------------------------------------------------------------
+// Delivery as a byte stream (k_offsets and k_concat; ops.h ConcatJob,
+// ConcatItem, ConcatRec)
+//
+// k_deliver without rows: the payloads back to back at byte offsets.  An
+// offset is the sum of every length before it, and the length of a packet
+// recovered in this submission exists only here, so the sum is made on the
+// device (frames.h concat_plan); the cursor has no row turn, so it is a plain
+// prefix sum and needs no serial walk.
+
+// k_offsets: one wave per job.  64 positions at a time, lane L takes position
+// k = b + L: an item (k < count) reads its first symbol dword (a 4-byte load at
+// the 16-byte aligned symbol) and computes n as k_deliver does, 0 for an
+// invalid packet; a position that is no item has n = 0.  The wave takes the
+// inclusive sum of n over its lanes (six __shfl_up steps, on 64-bit values:
+// 64 lengths of up to 2^29 - 1 pass 2^32) on top of the running sum of the
+// passes before, which is wave-uniform and 64-bit for the same reason.  A lane
+// stops the stream when it is no item, when its n is 0 or when its sum passes
+// the capacity; the first such lane, ctz of the ballot, is d, its exclusive sum
+// is B (every lane before it fits, so B <= capacity < 2^32) and its kind is the
+// stop reason.  Position count is no item, so every job stops.  Lanes before
+// the stop store their offset word and a record flagged kConcatWrite, lanes at
+// and behind it store B and a zero record, and the passes after the stop only
+// store.  Lane 0 writes the info record with one 16-byte store.  No LDS, no
+// atomics, no scratch.
+__global__ __launch_bounds__(64 * kDeliverWaves) void k_offsets(const ConcatJob* __restrict__ jobs, uint32_t jobCount,
+                                                                const ConcatItem* __restrict__ items,
+                                                                ConcatRec* __restrict__ recs)
+{
+    const uint32_t ji = __builtin_amdgcn_readfirstlane(blockIdx.x * kDeliverWaves + (threadIdx.x >> 6));
+    if (ji >= jobCount)
+        return;
+    const uint32_t lane = threadIdx.x & 63;
+    const ConcatJob jb = jobs[ji];
+    const uint64_t recBase = (uint64_t)(uintptr_t)(recs + jb.first);
+    uint64_t carry = 0;   // the sum of the passes before (wave-uniform)
+    bool stopped = false;
+    uint32_t d = 0, B = 0, stop = 0;
+    for (uint32_t b = 0; b <= jb.total; b += 64) {
+        const uint32_t k = b + lane;
+        const bool item = k < jb.count;
+        uint32_t n = 0, hs = 0, off = 0;
+        bool live = false;   // this lane's packet is delivered
+        if (!stopped) {      // (wave-uniform)
+            if (item) {
+                const ConcatItem it = items[jb.first + k];
+                if (it.cap != 0) {
+                    const uint32_t avail = it.cap < 4 ? it.cap : 4;
+                    const uint32_t w = *reinterpret_cast<const GMEM uint32_t*>(it.src) & byte_mask((int)avail);
+                    uint32_t len = 0;
+                    const int hh = parse_prefix(w, avail, &len);
+                    if (hh >= 1 && len >= 1 && (uint32_t)hh + len <= it.cap) {
+                        hs = (uint32_t)hh;
+                        n = len;
+                    }
+                }
+            }
+            uint32_t lo = n, hi = 0;
+#pragma unroll
+            for (unsigned s = 1; s < 64; s <<= 1) {
+                const uint32_t ulo = __shfl_up(lo, s), uhi = __shfl_up(hi, s);
+                if (lane >= s) {
+                    const uint64_t v = (((uint64_t)hi << 32) | lo) + (((uint64_t)uhi << 32) | ulo);
+                    lo = (uint32_t)v;
+                    hi = (uint32_t)(v >> 32);
+                }
+            }
+            const uint64_t incl = carry + (((uint64_t)hi << 32) | lo);
+            off = (uint32_t)(incl - n);   // (exact for every lane before the stop)
+            const uint64_t m = __ballot(!item || n == 0 || incl > (uint64_t)jb.capacity);
+            if (m) {
+                const uint32_t j = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(m));
+                stopped = true;
+                d = b + j;
+                B = __builtin_amdgcn_readlane(off, j);
+                stop = d >= jb.count ? 0u : __builtin_amdgcn_readlane(n, j) == 0 ? 1u : 2u;
+                live = lane < j;
+            } else {
+                live = true;
+                carry = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(incl >> 32), 63) << 32) |
+                        __builtin_amdgcn_readlane((uint32_t)incl, 63);
+            }
+        }
+        if (k <= jb.total)
+            *reinterpret_cast<GMEM uint32_t*>(jb.offsets + (uint64_t)k * 4) = live ? off : B;
+        if (item)
+            st16(recBase + (uint64_t)k * sizeof(ConcatRec),
+                 live ? make_uint4(off, n, hs, kConcatWrite) : make_uint4(0, 0, 0, 0));
+    }
+    if (lane == 0)
+        st16(jb.info, make_uint4(d, B, stop, jb.count));
+}
+
+// The bytes [b0, b1) of the aligned 16-byte word at `a`, from v, with stores no
+// wider than the bytes owned: a dword where all four are, else a short where
+// both are, else the byte.  The word's other bytes belong to a neighbouring
+// packet, whose wave writes them in the same launch, or to the caller: they are
+// neither read nor written.
+__device__ __forceinline__ void st_bytes(uint64_t a, uint4 v, uint32_t b0, uint32_t b1)
+{
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (unsigned i = 0; i < 4; ++i) {
+        const uint32_t at = 4 * i;
+        if (b0 <= at && at + 4 <= b1) {
+            *reinterpret_cast<GMEM uint32_t*>(a + at) = w[i];
+            continue;
+        }
+#pragma unroll
+        for (unsigned h = 0; h < 2; ++h) {
+            const uint32_t a2 = at + 2 * h;
+            const uint32_t y = w[i] >> (16 * h);
+            if (b0 <= a2 && a2 + 2 <= b1) {
+                *reinterpret_cast<GMEM uint16_t*>(a + a2) = (uint16_t)y;
+            } else {
+                if (b0 <= a2 && a2 < b1)
+                    *reinterpret_cast<GMEM uint8_t*>(a + a2) = (uint8_t)y;
+                if (b0 <= a2 + 1 && a2 + 1 < b1)
+                    *reinterpret_cast<GMEM uint8_t*>(a + a2 + 1) = (uint8_t)(y >> 8);
+            }
+        }
+    }
+}
+
+// k_concat: k_deliver's grid -- one wave per (item, 8 KiB chunk) -- over the
+// aligned 16-byte words of the destination that hold a byte of the payload.
+// D = dst + off has any alignment; positions p count from A0 = D rounded down
+// to 16, the payload is [dlo, dlo + n) there and lane L of each 1 KiB tile owns
+// the word at p = 16 L.  A word wholly inside the payload (the body) is one
+// 16-byte store.  The first and the last word may be partial -- a short packet
+// may lie inside one word, or straddle two and fill neither -- and are written
+// by st_bytes from the lane that holds them: never a load, merge and store of a
+// destination word, whose other bytes the neighbouring packet's wave writes in
+// this same launch.  The source byte that lands on A0 is src + hs - dlo; its
+// low four bits are the shift, uniform per item, and all sixteen occur (k_pack
+// sees 6..12), so the word select q = 0..3 is a uniform branch of four and the
+// byte shift r goes to v_alignbyte_b32 as a register.  Of the two aligned source
+// words around a destination word, one is loaded only if the bytes [b0, b1)
+// that the lane owns need a byte of it; those bytes are payload bytes, so
+// every load stays inside the aligned words that hold a byte of [src + hs,
+// src + hs + n), which k_offsets checked against cap.  Two tiles' loads are in
+// flight before their stores.  No LDS, no atomics, no scratch.
+__global__ __launch_bounds__(64 * kDeliverWaves) void k_concat(const ConcatJob* __restrict__ jobs,
+                                                               const ConcatItem* __restrict__ items,
+                                                               const ConcatRec* __restrict__ recs, uint32_t count)
+{
+    const uint32_t ii = __builtin_amdgcn_readfirstlane(blockIdx.x * kDeliverWaves + (threadIdx.x >> 6));
+    if (ii >= count)
+        return;
+    const uint32_t lane = threadIdx.x & 63;
+    const ConcatRec rc = recs[ii];
+    if (!(rc.flags & kConcatWrite))   // (uniform)
+        return;
+    const ConcatItem it = items[ii];
+    const uint64_t D = jobs[it.job].dst + rc.off;
+    const uint32_t dlo = (uint32_t)(D & 15u);
+    const uint64_t A0 = D - dlo;
+    const uint64_t total = (uint64_t)dlo + rc.n;          // from A0 to the payload's end
+    const uint64_t sbase = it.src + rc.hs - dlo;          // the source byte that lands on A0
+    const unsigned sh = (unsigned)(sbase & 15u);          // 0..15
+    const unsigned q = sh >> 2, r = sh & 3;
+    const uint64_t sa0 = sbase - sh;
+    const uint64_t step = (uint64_t)gridDim.y * kIngestChunkBytes;
+    for (uint64_t c0 = (uint64_t)blockIdx.y * kIngestChunkBytes; c0 < total; c0 += step) {
+        const uint64_t c1 = c0 + kIngestChunkBytes < total ? c0 + kIngestChunkBytes : total;
+        for (uint64_t t = c0; t < c1; t += 2 * kTileBytes) {
+            uint4 out[2];
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                out[u] = make_uint4(0, 0, 0, 0);
+                if (p >= total)
+                    continue;
+                const uint32_t b0 = p == 0 ? dlo : 0u;
+                const uint32_t b1 = total - p < 16 ? (uint32_t)(total - p) : 16u;
+                const uint4 lo = sh + b0 < 16 ? ld16(sa0 + p) : make_uint4(0, 0, 0, 0);
+                const uint4 hi = sh + b1 > 16 ? ld16(sa0 + p + 16) : make_uint4(0, 0, 0, 0);
+                const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                switch (q) {   // wave-uniform
+                case 0:
+                    out[u] = make_uint4(pick(w, 0, r, 0), pick(w, 0, r, 1), pick(w, 0, r, 2), pick(w, 0, r, 3));
+                    break;
+                case 1:
+                    out[u] = make_uint4(pick(w, 1, r, 0), pick(w, 1, r, 1), pick(w, 1, r, 2), pick(w, 1, r, 3));
+                    break;
+                case 2:
+                    out[u] = make_uint4(pick(w, 2, r, 0), pick(w, 2, r, 1), pick(w, 2, r, 2), pick(w, 2, r, 3));
+                    break;
+                default:
+                    out[u] = make_uint4(pick(w, 3, r, 0), pick(w, 3, r, 1), pick(w, 3, r, 2), pick(w, 3, r, 3));
+                    break;
+                }
+            }
+#pragma unroll
+            for (unsigned u = 0; u < 2; ++u) {
+                const uint64_t p = t + u * kTileBytes + lane * 16;
+                if (p >= total)
+                    continue;
+                const uint32_t b0 = p == 0 ? dlo : 0u;
+                const uint32_t b1 = total - p < 16 ? (uint32_t)(total - p) : 16u;
+                if (b0 == 0 && b1 == 16)
+                    st16(A0 + p, out[u]);
+                else
+                    st_bytes(A0 + p, out[u], b0, b1);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Row scan (k_scan, ops.h RowHead)
 //
 // The way in for frame rows that exist only in device memory: one lane per
@@ -5152,6 +5363,26 @@ void be_launch_pack(const PackJob* jobs, uint32_t jobCount, const PackItem* item
         std::min(kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxStride + kIngestChunkBytes - 1) / kIngestChunkBytes)));
     hipLaunchKernelGGL(k_pack, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
                        g_stream, jobs, items, (const PlanRec*)plan, count);
+}
+
+void be_launch_concat(const ConcatJob* jobs, uint32_t jobCount, const ConcatItem* items, uint32_t count,
+                      ConcatRec* recs, uint32_t maxBytes)
+{
+    if (jobCount == 0)
+        return;
+    {
+        Timed t(kBeOffsets);
+        hipLaunchKernelGGL(k_offsets, dim3((jobCount + kDeliverWaves - 1) / kDeliverWaves), dim3(64 * kDeliverWaves),
+                           0, g_stream, jobs, jobCount, items, recs);
+    }
+    if (count == 0)   // (jobs without items: their offset words and info records were all there is)
+        return;
+    Timed t(kBeConcat);
+    // (the grid of be_launch_deliver: a payload is shorter than its symbol, and starts up to 15 bytes into a word)
+    const uint32_t chunks = std::min(
+        kDeliverMaxChunks, std::max(1u, (uint32_t)(((uint64_t)maxBytes + 15 + kIngestChunkBytes - 1) / kIngestChunkBytes)));
+    hipLaunchKernelGGL(k_concat, dim3((count + kDeliverWaves - 1) / kDeliverWaves, chunks), dim3(64 * kDeliverWaves), 0,
+                       g_stream, jobs, items, (const ConcatRec*)recs, count);
 }
 
 void be_launch_exec(const void* stream, const ExecItem* items, uint32_t count, uint64_t* acct,

@@ -450,6 +450,27 @@ SIAMESE_EXPORT SiameseResult sgpu_decoder_pack_frames(SgpuDecoder decoder, unsig
     return r;
 }
 
+SIAMESE_EXPORT SiameseResult sgpu_decoder_deliver_stream(SgpuDecoder decoder, unsigned firstPacketNum, unsigned count,
+                                                         void* deviceDst, size_t capacity, unsigned* deviceOffsets,
+                                                         unsigned* deviceInfo, SiameseResult* results,
+                                                         unsigned* queuedOut)
+{
+    if (queuedOut)
+        *queuedOut = 0;
+    const uint64_t dst = (uint64_t)(uintptr_t)deviceDst, offsets = (uint64_t)(uintptr_t)deviceOffsets;
+    const uint64_t info = (uint64_t)(uintptr_t)deviceInfo;
+    // (deviceDst has any alignment: a receiver appends at its write cursor)
+    if (!decoder || !queuedOut || BD(decoder)->core.ge_pending() || !offsets || (offsets & 3u) != 0 || !info ||
+        (info & 15u) != 0 || (!deviceDst && capacity) || (uint64_t)capacity > 0xffffffffull ||
+        count > kConcatMaxItems || firstPacketNum > SIAMESE_PACKET_NUM_MAX)
+        return Siamese_InvalidInput;
+    unsigned queued = 0;
+    const SiameseResult r = BD(decoder)->core.deliver_stream(firstPacketNum, count, dst, (uint32_t)capacity, offsets,
+                                                             info, results, &queued);
+    *queuedOut = queued;
+    return r;
+}
+
 SIAMESE_EXPORT SiameseResult sgpu_decode_deferred(SgpuDecoder decoder, SiameseOriginalPacket* out,
                                                   unsigned capacity, unsigned* countOut)
 {
@@ -1122,15 +1143,16 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[29] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[30] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
                             s.geJobs,     s.geChained,   s.geRetried,  s.geChainedWide,
                             s.delivers,   s.frames,      s.scans,      Engine::global()->walks(),
                             s.relays,     Engine::global()->packs(),
-                            Engine::global()->duplexes(), Engine::global()->ack_frames()};
-    for (unsigned k = 0; k < count && k < 29; ++k)
+                            Engine::global()->duplexes(), Engine::global()->ack_frames(),
+                            Engine::global()->concats()};
+    for (unsigned k = 0; k < count && k < 30; ++k)
         out[k] = v[k];
 }
 

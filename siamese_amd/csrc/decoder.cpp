@@ -2837,6 +2837,39 @@ SiameseResult DecoderCore::pack_frames(unsigned firstNum, unsigned count, unsign
     return Siamese_Success;
 }
 
+SiameseResult DecoderCore::deliver_stream(unsigned firstNum, unsigned count, uint64_t dst, uint32_t capacity,
+                                          uint64_t offsets, uint64_t info, SiameseResult* results, unsigned* queued)
+{
+    *queued = 0;
+    settle();
+    if (dead())
+        return Siamese_Disabled;
+    // deliver_range's walk, up to the first absent packet: the stream cannot
+    // pass a hole.  A known length is not held against the capacity: a full
+    // buffer is a stop the device reports, not an error
+    std::vector<ConcatItem> items;
+    items.reserve(count);
+    unsigned e = column_to_element(firstNum);
+    for (unsigned k = 0; k < count; ++k, e = (e + 1) % kColumnPeriod) {
+        const DecSlot* s = e < count_ ? &slot(e) : nullptr;
+        if (!s || s->bytes == 0)
+            break;
+        // (a pending slot's bytes are its row's finalBytes, as in deliver_range)
+        ConcatItem it;
+        it.src = s->buf.addr();
+        it.cap = s->bytes;
+        it.job = 0;
+        items.push_back(it);
+    }
+    const unsigned p = (unsigned)items.size();
+    if (results)
+        for (unsigned k = 0; k < count; ++k)
+            results[k] = k < p ? Siamese_Success : Siamese_NeedMoreData;
+    *queued = p;
+    prog_.concat(items.data(), p, count, dst, capacity, offsets, info);
+    return Siamese_Success;
+}
+
 SiameseResult DecoderCore::decode_deferred(SiameseOriginalPacket* out, unsigned capacity, unsigned* countOut)
 {
     settle();

@@ -157,6 +157,14 @@ public:
     SiameseResult pack_frames(unsigned firstNum, unsigned count, unsigned flow, uint64_t dst, uint64_t stride,
                               unsigned maxRows, uint64_t lens, uint64_t info, SiameseResult* results,
                               unsigned* queued);
+    /// sgpu_decoder_deliver_stream: the payloads of the range's leading
+    /// present packets back to back in dst[0, capacity), summed and copied on
+    /// the device from the lengths it reads (Program::concat, frames.h
+    /// concat_plan): offsets gets count + 1 words, info four.  One item per
+    /// packet of that leading run (*queued of them); a packet behind the first
+    /// absent one gets Siamese_NeedMoreData and is no item.
+    SiameseResult deliver_stream(unsigned firstNum, unsigned count, uint64_t dst, uint32_t capacity, uint64_t offsets,
+                                 uint64_t info, SiameseResult* results, unsigned* queued);
     /// Host-memory recovery packet (drop-in API).
     SiameseResult add_recovery(const SiameseRecoveryPacket& packet);
     /// Device-resident recovery packet (batch API).

@@ -123,6 +123,7 @@ void ProgramBody::clear()
     frameLitRefs.clear();
     nrelay = 0;
     npackjob = npack = 0;
+    nconcatjob = nconcat = 0;
     gateOpen = false;
 }
 
@@ -965,6 +966,31 @@ void Program::pack(const PackItem* items, uint32_t count, uint64_t rows, uint64_
     b_->packJobs[b_->npackjob++] = jb;
 }
 
+void Program::concat(const ConcatItem* items, uint32_t count, uint32_t total, uint64_t dst, uint32_t capacity,
+                     uint64_t offsets, uint64_t info)
+{
+    touch();
+    ConcatJob jb;
+    jb.dst = dst;
+    jb.offsets = offsets;
+    jb.info = info;
+    jb.capacity = capacity;
+    jb.first = b_->nconcat;
+    jb.count = count;
+    jb.total = total;
+    if (b_->concats.size() < (size_t)b_->nconcat + count)
+        b_->concats.resize((size_t)b_->nconcat + count);
+    for (uint32_t k = 0; k < count; ++k) {
+        ConcatItem& it = b_->concats[b_->nconcat + k];
+        it = items[k];
+        it.job = b_->nconcatjob;
+    }
+    b_->nconcat += count;
+    if (b_->nconcatjob == b_->concatJobs.size())
+        b_->concatJobs.emplace_back();
+    b_->concatJobs[b_->nconcatjob++] = jb;
+}
+
 // ---------------------------------------------------------------------------
 // Shard queues
 
@@ -1519,6 +1545,10 @@ struct Batch
     size_t oPack = 0, nPack = 0;           // ... and their items (ops.h PackItem)
     size_t oPlan = 0;                      // ... k_plan's records: device side only, behind the upload
     uint32_t maxPackStride = 0;            // ... the jobs' longest row, as maxDeliverStride (k_pack's grid)
+    size_t oConcatJob = 0, nConcatJob = 0; // stream jobs of every body (ops.h ConcatJob)
+    size_t oConcat = 0, nConcat = 0;       // ... and their items (ops.h ConcatItem)
+    size_t oConcatRec = 0;                 // ... k_offsets' records: device side only, behind k_plan's
+    uint32_t maxConcatBytes = 0;           // ... the items' longest symbol (k_concat's grid)
     size_t oCopy = 0;                      // the download copy list (BeCopy records)
     uint64_t wideBase = 0;                 // this submission's k_ldpc scratch: bytes into the ring
     bool wideGated = false;                // k_ldpc items of gated ops: the launches take the gate
@@ -2265,6 +2295,7 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     size_t frameLitBytes = 0;   // and the bytes they carry themselves
     size_t nRelay = 0;     // relay items of every body
     size_t nPackJob = 0, nPack = 0;   // pack jobs and items of every body
+    size_t nConcatJob = 0, nConcat = 0;   // stream jobs and items of every body
     for (int g = 0; g < 2; ++g)
         for (size_t pi = 0; pi < bt.bodies[g].size(); ++pi) {
             const ProgramBody* p = bt.bodies[g][pi];
@@ -2274,6 +2305,8 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
             nRelay += p->nrelay;
             nPackJob += p->npackjob;
             nPack += p->npack;
+            nConcatJob += p->nconcatjob;
+            nConcat += p->nconcat;
             for (size_t k = 0; k < p->nges; ++k) {
                 const ProgramBody::PendingGe& ge = p->ges[k];
                 GeDesc d;
@@ -2312,6 +2345,8 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     bt.nRelay = nRelay;
     bt.nPackJob = nPackJob;
     bt.nPack = nPack;
+    bt.nConcatJob = nConcatJob;
+    bt.nConcat = nConcat;
 
     constexpr size_t kIngestChunk = SGPU_INGEST_CHUNK;
     size_t nIngest = 0, stageBytes = 0, nIngBlocks = 0;
@@ -2387,6 +2422,11 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     off = align16(off + nPackJob * sizeof(PackJob));
     bt.oPack = off;
     off = align16(off + nPack * sizeof(PackItem));
+    // the stream jobs and their items (k_offsets and k_concat beside them)
+    bt.oConcatJob = off;
+    off = align16(off + nConcatJob * sizeof(ConcatJob));
+    bt.oConcat = off;
+    off = align16(off + nConcat * sizeof(ConcatItem));
     // the frame items' own bytes (Program::frame_literal)
     const size_t oFrameLit = off;
     off = align16(off + frameLitBytes);
@@ -2400,8 +2440,10 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     // k_plan's records lie behind the upload in its device copy: written and
     // read on the device only, never uploaded
     bt.oPlan = off;
+    // ... and k_offsets' behind them, on the same terms
+    bt.oConcatRec = bt.oPlan + nPack * sizeof(PlanRec);
     if (bt.upBytes)
-        ensure_up(xs, bt.upBytes + nPack * sizeof(PlanRec));
+        ensure_up(xs, bt.oConcatRec + nConcat * sizeof(ConcatRec));
     // A small upload is not copied: the kernels read it from the pinned
     // buffer over the bus (zero-copy), which skips a copy and its hand-off
     // on the latency-bound paths (SIAMESE_AMD_ZEROCOPY_UP bytes at most,
@@ -2659,6 +2701,29 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
             }
         bt.maxPackStride = (uint32_t)std::min<uint64_t>((uint64_t)max16 << 4, 0xffffffffu);
     }
+    if (nConcatJob) {
+        ConcatJob* cj = (ConcatJob*)(up + bt.oConcatJob);
+        ConcatItem* ci = (ConcatItem*)(up + bt.oConcat);
+        uint32_t maxCap = 0, jobBase = 0, itemBase = 0;
+        for (int g = 0; g < 2; ++g)
+            for (const ProgramBody* p : bt.bodies[g]) {
+                if (p->nconcatjob == 0)
+                    continue;
+                // (a body's indices become the launch's)
+                for (uint32_t k = 0; k < p->nconcatjob; ++k) {
+                    cj[jobBase + k] = p->concatJobs[k];
+                    cj[jobBase + k].first += itemBase;
+                }
+                for (uint32_t k = 0; k < p->nconcat; ++k) {
+                    ci[itemBase + k] = p->concats[k];
+                    ci[itemBase + k].job += jobBase;
+                    maxCap = std::max(maxCap, ci[itemBase + k].cap);
+                }
+                jobBase += p->nconcatjob;
+                itemBase += p->nconcat;
+            }
+        bt.maxConcatBytes = maxCap;
+    }
 
     // download area: the byte counters (kAcctBytes), the solve results, then
     // each requested range
@@ -2690,7 +2755,8 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
 
     st.flushes = 1;
     st.launches = phases.size() + (nIngest ? 1 : 0) + (gdescs.empty() ? 0 : 1) + (nDeliver ? 1 : 0) +
-                  (nFrame ? 1 : 0) + (nRelay ? 1 : 0) + (nPackJob ? 1 : 0) + (nPack ? 1 : 0);
+                  (nFrame ? 1 : 0) + (nRelay ? 1 : 0) + (nPackJob ? 1 : 0) + (nPack ? 1 : 0) +
+                  (nConcatJob ? 1 : 0) + (nConcat ? 1 : 0);
     st.delivers = nDeliver;
     st.frames = nFrame;
     st.relays = nRelay;
@@ -2828,6 +2894,14 @@ void Engine::launch_batch(Batch& bt)
         be_launch_pack((const PackJob*)(bt.upBase + bt.oPackJob), (uint32_t)bt.nPackJob,
                        (const PackItem*)(bt.upBase + bt.oPack), (uint32_t)bt.nPack, (PlanRec*)(xs.upDev + bt.oPlan),
                        bt.maxPackStride);
+    }
+    // ... and its stream jobs, likewise: k_offsets sums the lengths where the
+    // solve left them, k_concat copies to the offsets it wrote
+    if (bt.nConcatJob) {
+        concats_.fetch_add(bt.nConcat, std::memory_order_relaxed);
+        be_launch_concat((const ConcatJob*)(bt.upBase + bt.oConcatJob), (uint32_t)bt.nConcatJob,
+                         (const ConcatItem*)(bt.upBase + bt.oConcat), (uint32_t)bt.nConcat,
+                         (ConcatRec*)(xs.upDev + bt.oConcatRec), bt.maxConcatBytes);
     }
     // the counters and solve results, then the downloads, in one call (one
     // kernel when small; its range list was laid out with the upload: a

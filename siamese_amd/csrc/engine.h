@@ -378,6 +378,14 @@ struct ProgramBody
     std::vector<PackJob> packJobs;
     std::vector<PackItem> packs;
     uint32_t npackjob = 0, npack = 0;
+    /// A decoder's packets to deliver as one byte stream (ops.h ConcatJob,
+    /// ConcatItem): one job per Program::concat call, its items behind those
+    /// of the job before; first and job are relative to this body until
+    /// assembly.  Run by the submission's k_offsets and k_concat launches
+    /// beside k_deliver's.  nconcatjob and nconcat in use (capacity is kept).
+    std::vector<ConcatJob> concatJobs;
+    std::vector<ConcatItem> concats;
+    uint32_t nconcatjob = 0, nconcat = 0;
     void lc_seal();                     // seals the open OP_LINCOMBS batch
     /// Move the segment's last op (an OP_LINCOMB) into the open batch, or
     /// seal the batch first when they are not independent.
@@ -388,6 +396,7 @@ struct ProgramBody
     bool empty() const
     {
         return nges == 0 && ndeliver == 0 && nframe == 0 && nrelay == 0 && npackjob == 0 &&
+               nconcatjob == 0 &&
                (nsegs == 0 ||
                 (nsegs == 1 && segs[0].ops.empty() && copies.empty() && lcb.items.empty() && !rb.open));
     }
@@ -582,6 +591,17 @@ public:
     /// program whose only work is pack jobs still makes a submission.
     void pack(const PackItem* items, uint32_t count, uint64_t rows, uint64_t stride, uint32_t maxRows, uint64_t lens,
               uint64_t info);
+
+    /// Queue one stream job (ops.h ConcatJob) and its items: items[k] holds
+    /// packet k's symbol and capacity, k < count, the leading present packets
+    /// of a range of `total` (job is set here).  The device sums their lengths,
+    /// copies the payloads back to back into dst[0, capacity) and writes
+    /// offsets[0, total] and the four words at info (k_offsets, k_concat).
+    /// Ordered as deliver()'s items.  A job without items still writes its
+    /// offset words and info record, and a program whose only work is stream
+    /// jobs still makes a submission.
+    void concat(const ConcatItem* items, uint32_t count, uint32_t total, uint64_t dst, uint32_t capacity,
+                uint64_t offsets, uint64_t info);
 
     bool empty() const { return !b_ || b_->empty(); }
 
@@ -936,10 +956,13 @@ private:
     // (sgpu_decoders_ack_frames), counted by the call ([28]); here for the same reason
     std::atomic<uint64_t> duplexes_{0};
     std::atomic<uint64_t> ackFrames_{0};
+    // stream items queued (sgpu_decoder_deliver_stream), counted as packs_ ([29]); here for the same reason
+    std::atomic<uint64_t> concats_{0};
 
 public:
     uint64_t walks() const { return walks_.load(std::memory_order_relaxed); }
     uint64_t packs() const { return packs_.load(std::memory_order_relaxed); }
+    uint64_t concats() const { return concats_.load(std::memory_order_relaxed); }
     uint64_t duplexes() const { return duplexes_.load(std::memory_order_relaxed); }
     uint64_t ack_frames() const { return ackFrames_.load(std::memory_order_relaxed); }
     void count_ack_frames(uint64_t n) { ackFrames_.fetch_add(n, std::memory_order_relaxed); }

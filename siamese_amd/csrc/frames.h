@@ -456,4 +456,62 @@ inline void pack_plan(const uint8_t* const* syms, const uint32_t* caps, uint32_t
     info[3] = frames - written;
 }
 
+/// What k_offsets computes for one job (ops.h ConcatJob): syms[k] is packet k's
+/// symbol (null: absent), of which caps[k] bytes may be read.  p = the leading
+/// non-null syms: the stream cannot reach a packet behind a hole.  Packet k < p
+/// has prefix bytes hs and length n, and is valid as k_deliver judges it: the
+/// prefix can be read from min(cap, 4) bytes, n >= 1 and hs + n <= cap.  With
+/// off_0 = 0, packet k is delivered when every packet before it was, it is
+/// valid and off_k + n <= capacity; then off_{k+1} = off_k + n.  d = the packets
+/// delivered, B = off_d.  offsets[k] = off_k for k <= d and B for d < k <=
+/// count; recs[k], k < p, is {off_k, n, hs, kConcatWrite} for k < d and zero
+/// otherwise; info = {d, B, stop, p} with stop 0 when d == p, 1 when packet d
+/// is invalid and 2 when it is valid and does not fit.  The sums are 64-bit:
+/// 65535 lengths of up to 2^29 - 1 pass 2^32.  Reads only syms[k][0,
+/// min(caps[k], 4)), writes only offsets[0, count], recs[0, p) and info[0, 4).
+inline void concat_plan(const uint8_t* const* syms, const uint32_t* caps, uint32_t count, uint64_t capacity,
+                        uint32_t* offsets, ConcatRec* recs, uint32_t* info)
+{
+    uint32_t p = 0;
+    while (p < count && syms[p])
+        ++p;
+    uint64_t off = 0;
+    uint32_t d = 0, stop = 0;
+    for (; d < p; ++d) {
+        unsigned length = 0;
+        const int h = read_length_prefix(syms[d], caps[d] < 4 ? caps[d] : 4u, &length);
+        if (h < 1 || length < 1 || (uint64_t)h + length > caps[d]) {
+            stop = 1;
+            break;
+        }
+        if (off + length > capacity) {
+            stop = 2;
+            break;
+        }
+        offsets[d] = (uint32_t)off;
+        recs[d].off = (uint32_t)off;
+        recs[d].n = length;
+        recs[d].hs = (uint32_t)h;
+        recs[d].flags = kConcatWrite;
+        off += length;
+    }
+    for (uint32_t k = d; k <= count; ++k)
+        offsets[k] = (uint32_t)off;
+    for (uint32_t k = d; k < p; ++k)
+        std::memset(&recs[k], 0, sizeof(ConcatRec));
+    info[0] = d;
+    info[1] = (uint32_t)off;
+    info[2] = stop;
+    info[3] = p;
+}
+
+/// What k_concat computes for one record with kConcatWrite: dst[rec.off,
+/// rec.off + rec.n) = sym[rec.hs, rec.hs + rec.n), dst the job's stream at any
+/// byte alignment.  No other byte is written, or read.
+inline void concat_copy(const uint8_t* sym, const ConcatRec& rec, uint8_t* dst)
+{
+    if (rec.flags & kConcatWrite)
+        std::memcpy(dst + rec.off, sym + rec.hs, rec.n);
+}
+
 } // namespace sgpu

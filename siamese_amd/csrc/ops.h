@@ -526,6 +526,56 @@ constexpr uint32_t kPackMaxItems = 65535;   // items of one job
 /// grid is k_deliver's over the items, the chunk rows sized by the longest
 /// stride (a span is at most a row).
 
+/// A decoder's packets as one contiguous byte stream (k_offsets and k_concat,
+/// sgpu_decoder_deliver_stream).  One ConcatJob per call, one ConcatItem per
+/// packet of the range's leading present run (count = p of them; the range has
+/// `total` packets), in packet order; k_offsets writes one ConcatRec per item
+/// into scratch of the submission, k_concat reads it.
+///
+/// An item's payload is DeliverItem's: hs and n from the symbol's first bytes,
+/// valid when n >= 1 and hs + n <= cap.  k_offsets sums the job's n in item
+/// order (frames.h concat_plan): off_0 = 0, item k is delivered when every item
+/// before it was, it is valid and off_k + n <= capacity, and then off_{k+1} =
+/// off_k + n.  With d items delivered and B = off_d it writes the job's
+/// total + 1 offset words (off_k for k <= d, B behind) and info = {d, B, stop,
+/// count}, stop 0 for d == count, 1 for an invalid item d, 2 for one that does
+/// not fit.  k_concat writes dst[off, off + n) = src[hs, hs + n) of every record
+/// flagged kConcatWrite, dst at any byte alignment, and no other byte: words
+/// that two neighbouring packets share are written by byte-granular stores and
+/// never read.  Only aligned 16-byte words holding a byte of [src, src + cap)
+/// are read.
+struct ConcatItem
+{
+    uint64_t src;        // the symbol, 16-byte aligned (never 0: only present packets are items)
+    uint32_t cap;        // as DeliverItem.cap
+    uint32_t job;        // index of the item's ConcatJob in the launch
+};
+static_assert(sizeof(ConcatItem) == 16, "ConcatItem layout");
+struct ConcatJob
+{
+    uint64_t dst;        // the stream's byte 0, any alignment (not read when capacity = 0)
+    uint64_t offsets;    // total + 1 uint32 offset words, 4-byte aligned
+    uint64_t info;       // four uint32, 16-byte aligned
+    uint32_t capacity;   // bytes the caller owns at dst
+    uint32_t first;      // index of the job's first item in the launch
+    uint32_t count;      // its items (<= total)
+    uint32_t total;      // packets of the call's range (<= 65535)
+};
+static_assert(sizeof(ConcatJob) == 40, "ConcatJob layout");
+struct ConcatRec
+{
+    uint32_t off;        // the payload's offset in the stream
+    uint32_t n;          // its bytes
+    uint32_t hs;         // the symbol's prefix bytes (1..4)
+    uint32_t flags;      // kConcatWrite, or 0: not delivered
+};
+static_assert(sizeof(ConcatRec) == 16, "ConcatRec layout");
+constexpr uint32_t kConcatWrite = 1;
+constexpr uint32_t kConcatMaxItems = 65535;   // packets of one job
+/// k_offsets runs one wave per job, kDeliverWaves jobs per workgroup; k_concat's
+/// grid is k_deliver's over the items, the chunk rows sized by the longest
+/// symbol (a payload is shorter than its symbol).
+
 /// What the host needs of one frame row that lives in device memory (k_scan,
 /// sgpu_frames_scan_rows): the layout of SgpuRowHead (include/siamese_gpu.h),
 /// written as eight dwords

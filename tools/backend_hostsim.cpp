@@ -549,6 +549,35 @@ void be_launch_pack(const PackJob* jobs, uint32_t jobCount, const PackItem* item
     }
 }
 
+// k_offsets and k_concat (ops.h ConcatJob, ConcatItem, ConcatRec): frames.h
+// concat_plan for every job, then concat_copy for every record it flagged.
+void be_launch_concat(const ConcatJob* jobs, uint32_t jobCount, const ConcatItem* items, uint32_t count,
+                      ConcatRec* recs, uint32_t)
+{
+    if (noexec())
+        return;
+    for (uint32_t j = 0; j < jobCount; ++j) {
+        const ConcatJob& jb = jobs[j];
+        // (the packets behind the leading present run are no items: holes to the plan)
+        std::vector<const uint8_t*> syms(jb.total, nullptr);
+        std::vector<uint32_t> caps(jb.total, 0);
+        for (uint32_t k = 0; k < jb.count; ++k) {
+            const ConcatItem& it = items[jb.first + k];
+            syms[k] = P(it.src);
+            caps[k] = it.cap;
+        }
+        std::vector<uint32_t> offsets((size_t)jb.total + 1);
+        uint32_t info[4];
+        concat_plan(syms.data(), caps.data(), jb.total, jb.capacity, offsets.data(), recs + jb.first, info);
+        std::memcpy(P(jb.offsets), offsets.data(), offsets.size() * 4);
+        std::memcpy(P(jb.info), info, sizeof(info));
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        const ConcatItem& it = items[i];
+        concat_copy(P(it.src), recs[i], P(jobs[it.job].dst));
+    }
+}
+
 static void solve_prefix(const SolveDesc* solves, const SolveRow* rows, const uint8_t* coef,
                             uint32_t* results, uint32_t count, uint64_t* acct)
 {

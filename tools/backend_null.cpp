@@ -88,6 +88,7 @@ void be_launch_deliver(const DeliverItem*, uint32_t, uint32_t) {}
 void be_launch_frame(const FrameItem*, uint32_t, uint32_t) {}
 void be_launch_relay(const RelayItem*, uint32_t, uint32_t) {}
 void be_launch_pack(const PackJob*, uint32_t, const PackItem*, uint32_t, PlanRec*, uint32_t) {}
+void be_launch_concat(const ConcatJob*, uint32_t, const ConcatItem*, uint32_t, ConcatRec*, uint32_t) {}
 
 static void solve_prefix(const SolveDesc* solves, const SolveRow*, const uint8_t*,
                             uint32_t* results, uint32_t count, uint64_t*)
