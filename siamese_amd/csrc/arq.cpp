@@ -188,7 +188,7 @@ void EncoderCore::update_rto()
         element = firstUnremoved_;
 
     auto sample = [&](unsigned e) {
-        const int32_t delay = (int32_t)(now - slot(e).lastSend);
+        const int32_t delay = (int32_t)(now - peek(e).lastSend);
         if ((unsigned)delay > longest && delay > 0)
             longest = (unsigned)delay;
     };
@@ -302,7 +302,7 @@ SiameseResult EncoderCore::retransmit(SiameseOriginalPacket& out)
     if (ack_.foundOldest) {
         const unsigned e = column_sub(ack_.oldestColumn, columnStart_);
         if (!column_delta_negative(e) && e >= first && e < count) {
-            EncSlot& s = slot(e);
+            EncSlot& s = slot(e, kDemoteArq);
             if ((uint32_t)(now - s.lastSend) < rto)
                 return Siamese_NeedMoreData;
             s.lastSend = now;
@@ -313,7 +313,7 @@ SiameseResult EncoderCore::retransmit(SiameseOriginalPacket& out)
     }
 
     unsigned nack = first;
-    EncSlot* oldest = &slot(nack);
+    EncSlot* oldest = &slot(nack, kDemoteArq);
     uint32_t oldestSend = oldest->lastSend;
     if ((uint32_t)(now - oldestSend) >= rto) {
         oldest->lastSend = now;
@@ -327,7 +327,7 @@ SiameseResult EncoderCore::retransmit(SiameseOriginalPacket& out)
             nack = column_to_element(column);
             if (nack >= count)
                 break;
-            EncSlot& s = slot(nack);
+            EncSlot& s = slot(nack, kDemoteArq);
             if ((uint32_t)(now - s.lastSend) >= rto) {
                 s.lastSend = now;
                 return retransmit_slot(s, out);
@@ -339,7 +339,7 @@ SiameseResult EncoderCore::retransmit(SiameseOriginalPacket& out)
         }
     }
     for (unsigned e = nack + 1; e < count; ++e) {
-        EncSlot& s = slot(e);
+        EncSlot& s = slot(e, kDemoteArq);
         if ((uint32_t)(now - s.lastSend) >= rto) {
             s.lastSend = now;
             return retransmit_slot(s, out);

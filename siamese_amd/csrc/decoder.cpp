@@ -59,6 +59,29 @@ struct WalkCounts
 #define SGPU_WALK_VISIT(field) ((void)0)
 #endif
 
+// Slot bookkeeping of all decoders of the process (the encoders' is in
+// encoder.cpp), printed at exit when SIAMESE_AMD_SLOT_COUNTS is set (read
+// once).  Each decoder counts for itself and adds its counts here when it is freed.
+constexpr unsigned kDecSlotCauses = 5;
+const char* const kDecSlotCauseNames[kDecSlotCauses] = {"add", "length", "stride", "matrix", "other"};
+struct DecSlotCounts
+{
+    const bool on = std::getenv("SIAMESE_AMD_SLOT_COUNTS") != nullptr;
+    std::atomic<uint64_t> decoders{0}, uniform{0}, writes{0};
+    std::atomic<uint64_t> demote[kDecSlotCauses] = {};
+    ~DecSlotCounts()
+    {
+        if (!on)
+            return;
+        std::fprintf(stderr, "dec slot counts: decoders %llu dec_uniform %llu dec_slot_writes %llu",
+                     (unsigned long long)decoders.load(), (unsigned long long)uniform.load(),
+                     (unsigned long long)writes.load());
+        for (unsigned c = 0; c < kDecSlotCauses; ++c)
+            std::fprintf(stderr, " dec_demote_%s %llu", kDecSlotCauseNames[c], (unsigned long long)demote[c].load());
+        std::fprintf(stderr, "\n");
+    }
+} g_decSlots;
+
 } // namespace
 
 DecoderCore::DecoderCore(Engine* eng, bool hostMirror)
@@ -219,19 +242,29 @@ DecoderCore::~DecoderCore()
     // one pass over each subwindow: release the buffers slots own and leave
     // every slot fresh, so the pool's recycle (DecSubwindowRecycle) need not
     // walk them again (a decoder's teardown is memory-bound on these slots)
+    // (a uniform subwindow, or one never written, has fresh slots already)
     for (auto& sw : subwindows_) {
-        for (DecSlot& s : sw->slot) {
-            if (!s.inSlab)
-                eng_->release(s.buf);
-            s.buf = DevBuf();
-            s.inSlab = false;
-            s.bytes = 0;
-            s.column = 0;
-            s.header = 0;
-            s.pending = false;
-            if (s.hostp)
-                s.hostp->clear();
+        if (sw->uni.mask) {
+#ifdef SGPU_SLOT_CHECK
+            slot_check(sw.get(), "teardown");
+            for (DecSlot& s : sw->shadow)
+                s = DecSlot();
+#endif
+            sw->uni = DecUniform();
         }
+        if (!sw->clean)
+            for (DecSlot& s : sw->slot) {
+                if (!s.inSlab)
+                    eng_->release(s.buf);
+                s.buf = DevBuf();
+                s.inSlab = false;
+                s.bytes = 0;
+                s.column = 0;
+                s.header = 0;
+                s.pending = false;
+                if (s.hostp)
+                    s.hostp->clear();
+            }
         sw->got = 0;
         sw->gotCount = 0;
         eng_->slab_release(sw->slab);
@@ -243,6 +276,14 @@ DecoderCore::~DecoderCore()
             eng_->release(s.d.buf);
     if (geState_ == 2)
         chain_sums_commit();   // (a chained decode never finished: its replaced sum buffers)
+    static_assert(kDemoteCauses == kDecSlotCauses, "a name for every cause");
+    if (g_decSlots.on) {
+        g_decSlots.decoders.fetch_add(1, std::memory_order_relaxed);
+        g_decSlots.uniform.fetch_add(uniformEntered_, std::memory_order_relaxed);
+        g_decSlots.writes.fetch_add(slotWrites_, std::memory_order_relaxed);
+        for (unsigned c = 0; c < kDecSlotCauses; ++c)
+            g_decSlots.demote[c].fetch_add(demotions_[c], std::memory_order_relaxed);
+    }
     donate_spare();
 }
 
@@ -323,7 +364,7 @@ bool DecoderCore::grow_window(unsigned end)
     const unsigned needed = (end + kLanes + kSubwindow - 1) / kSubwindow;
     while (subwindows_.size() < needed) {
         subwindows_.emplace_back(ObjPool<DecSubwindow>::get());
-        subwindows_.back()->clean = false;
+        subwindows_.back()->clean = true;   // (the pool's objects are fresh)
         ++windowGen_;
     }
     if (end > count_) {
@@ -333,9 +374,154 @@ bool DecoderCore::grow_window(unsigned end)
     return true;
 }
 
+void DecoderCore::demote(DecSubwindow* sw, DemoteCause cause)
+{
+#ifdef SGPU_SLOT_CHECK
+    slot_check(sw, "demote");
+    for (DecSlot& s : sw->shadow)
+        s = DecSlot();
+#endif
+    const DecUniform u = sw->uni;
+    for (uint64_t m = u.mask; m; m &= m - 1) {
+        const unsigned bit = (unsigned)__builtin_ctzll(m);
+        DecSlot& s = sw->slot[bit];
+        s.buf.ptr = sw->slab.buf.ptr + (size_t)bit * sw->slab.stride;
+        s.buf.cap = sw->slab.stride;
+        s.inSlab = true;
+        s.bytes = u.bytes;
+        s.header = u.header;
+        s.column = column_add(u.first, bit);
+        s.pending = false;
+    }
+    sw->uni = DecUniform();
+    sw->clean = false;
+    slotWrites_ += (unsigned)__builtin_popcountll(u.mask);
+    ++demotions_[cause];
+}
+
+#ifdef SGPU_SLOT_CHECK
+void DecoderCore::slot_check_failed(const char* where, const char* what, unsigned bit)
+{
+    std::fprintf(stderr, "SGPU_SLOT_CHECK: decoder %s: slot %u: %s differs from the per-element record\n", where, bit,
+                 what);
+    std::abort();
+}
+
+void DecoderCore::slot_check(const DecSubwindow* sw, const char* where) const
+{
+    const DecUniform& u = sw->uni;
+    if (!sw->clean)
+        slot_check_failed(where, "clean", 0);
+    if ((u.mask & sw->got) != u.mask)
+        slot_check_failed(where, "got", 0);
+    for (unsigned bit = 0; bit < kSubwindow; ++bit) {
+        const DecSlot& sh = sw->shadow[bit];
+        const DecSlot& real = sw->slot[bit];
+        if (real.buf.ptr || real.buf.cap || real.inSlab || real.bytes || real.column || real.header || real.pending)
+            slot_check_failed(where, "fresh slot[]", bit);
+        if (!(u.mask >> bit & 1u)) {
+            if (sh.buf.ptr || sh.bytes || sh.inSlab)
+                slot_check_failed(where, "mask", bit);
+            continue;
+        }
+        if (sh.buf.ptr != sw->slab.buf.ptr + (size_t)bit * sw->slab.stride)
+            slot_check_failed(where, "buf.ptr", bit);
+        if (sh.buf.cap != sw->slab.stride)
+            slot_check_failed(where, "buf.cap", bit);
+        if (!sh.inSlab)
+            slot_check_failed(where, "inSlab", bit);
+        if (!(sw->slab.used >> bit & 1u))
+            slot_check_failed(where, "slab.used", bit);
+        if (sh.bytes != u.bytes)
+            slot_check_failed(where, "bytes", bit);
+        if (sh.header != u.header)
+            slot_check_failed(where, "header", bit);
+        if (sh.column != column_add(u.first, bit))
+            slot_check_failed(where, "column", bit);
+        if (sh.pending)
+            slot_check_failed(where, "pending", bit);
+    }
+}
+#endif
+
+bool DecoderCore::uniform_takes(DecSubwindow* sw, unsigned element, unsigned m, unsigned need, unsigned h,
+                                unsigned column)
+{
+    if (mirror_ || !sw->clean)
+        return false;
+    const unsigned bit = element % kSubwindow;
+    const DecUniform& u = sw->uni;
+    if (!u.mask)   // fresh: no slab yet, and one that slab_slot will grant
+        return !sw->slab.buf && slab_stride(need) != 0;
+    // (one cause per demotion, the first that applies)
+    if (need > sw->slab.stride)
+        demote(sw, kDemoteStride);
+    else if (u.bytes != need || u.header != h || column_add(u.first, bit) != column)
+        demote(sw, kDemoteLength);
+    else if (sw->slab.used & run_bits(bit, m))
+        demote(sw, kDemoteAdd);
+    else
+        return true;
+    return false;
+}
+
+void DecoderCore::add_uniform(DecSubwindow* sw, unsigned element, unsigned m, unsigned need, unsigned h,
+                              unsigned bytes, unsigned column)
+{
+    const unsigned bit = element % kSubwindow;
+    const uint64_t bits = run_bits(bit, m);
+#ifdef SGPU_SLOT_CHECK
+    // the per-element code's records into the shadow
+    for (unsigned j = 0; j < m; ++j) {
+        DecSlot& sh = sw->shadow[bit + j];
+        if (sh.buf.ptr || sh.bytes || (sw->got >> (bit + j) & 1u))
+            slot_check_failed("add_original_range", "slot written before", bit + j);
+        uint8_t hd[kMaxLengthPrefix];
+        sh.buf.ptr = sw->slab.buf.ptr + (size_t)(bit + j) * sw->slab.stride;
+        sh.buf.cap = sw->slab.stride;
+        sh.inSlab = true;
+        sh.header = write_length_prefix(bytes, hd);
+        sh.bytes = sh.header + bytes;
+        sh.column = column_add(column, j);
+        sh.pending = false;
+        if (column_to_element(sh.column) != element + j)
+            slot_check_failed("add_original_range", "column", bit + j);
+    }
+#endif
+    sw->slab.used |= bits;
+    if (!sw->uni.mask) {
+        sw->uni.bytes = need;
+        sw->uni.header = h;
+        sw->uni.first = column_sub(column, bit);
+        ++uniformEntered_;
+    }
+    sw->uni.mask |= bits;
+    // what accept_original does for each of the m.  The region's test is
+    // made against the region as it stands: a reset is all that a hit or
+    // list_delete_before can do to it, and a reset region is hit by nothing.
+    const bool inRegion = element < region_.nextCheckStart && element + m > region_.elementStart;
+    sw->gotCount += m;
+    sw->got |= bits;
+    windowGen_ += m;
+    if (nextExpected_ >= element && nextExpected_ < element + m) {
+        // (the elements between it and the run's end are received: the next
+        // lost one is what the per-element walk ends on)
+        iterate_next_expected(nextExpected_ + 1);
+        list_delete_before(nextExpected_);
+    }
+    if (inRegion)
+        region_reset();
+    stats_[SiameseDecoderStats_OriginalCount] += m;
+    stats_[SiameseDecoderStats_OriginalBytes] += (uint64_t)m * bytes;
+}
+
 bool DecoderCore::place(unsigned element, unsigned need)
 {
     DecSubwindow* sw = subwindows_[element / kSubwindow].get();
+    if (sw->uni.mask)
+        demote(sw, kDemoteAdd);
+    sw->clean = false;
+    ++slotWrites_;
     DecSlot& s = sw->slot[element % kSubwindow];
     release_slot(s);
     bool failed = false;
@@ -388,7 +574,7 @@ SiameseResult DecoderCore::add_original(const SiameseOriginalPacket& packet, uin
         return Siamese_DuplicateData;
     }
     grow_window(element + 1);
-    DecSlot& s = slot(element);
+    DecSlot& s = slot(element, kDemoteAdd);
     if (s.bytes > 0) {
         stats_[SiameseDecoderStats_DupedOriginalCount]++;
         return Siamese_DuplicateData;
@@ -430,8 +616,30 @@ SiameseResult DecoderCore::add_original_range(unsigned firstNum, uint64_t src, u
             prog_.ingest_run(run.dst, run.stride, run.src, srcStride, run.n, run.bytes, run.hdr, run.h);
         run.n = 0;
     };
+    // `n` symbols of one length into consecutive slots of `cap` bytes from
+    // dst: the runs the per-element code makes of them (<= kIngestRunMax each)
+    auto append = [&](uint64_t dst, uint32_t cap, uint64_t from, unsigned bytes, unsigned h, const uint8_t* hdr,
+                      unsigned n) {
+        while (n) {
+            if (!(run.n && run.bytes == bytes && run.n < kIngestRunMax && cap == run.stride &&
+                  dst == run.dst + (uint64_t)run.n * run.stride && from == run.src + (uint64_t)run.n * srcStride)) {
+                close_run();
+                run.dst = dst;
+                run.src = from;
+                run.stride = cap;
+                run.bytes = bytes;
+                run.h = h;
+                std::memcpy(run.hdr, hdr, kMaxLengthPrefix);
+            }
+            const unsigned t = std::min<unsigned>(n, kIngestRunMax - run.n);
+            run.n += t;
+            dst += (uint64_t)t * cap;
+            from += (uint64_t)t * srcStride;
+            n -= t;
+        }
+    };
     SiameseResult res = Siamese_Success;
-    for (unsigned k = 0; k < count; ++k) {
+    for (unsigned k = 0; k < count;) {
         const unsigned num = (firstNum + k) & SIAMESE_PACKET_NUM_MAX;
         const unsigned bytes = lens ? lens[k] : fixedBytes;
         SiameseResult r = Siamese_Success;
@@ -444,37 +652,64 @@ SiameseResult DecoderCore::add_original_range(unsigned firstNum, uint64_t src, u
             r = Siamese_DuplicateData;
         else {
             grow_window(element + 1);
-            if (slot(element).bytes > 0)
+            if (peek_bytes(element) > 0)
                 r = Siamese_DuplicateData;
         }
         if (r == Siamese_DuplicateData)
             stats_[SiameseDecoderStats_DupedOriginalCount]++;
         if (r == Siamese_Success) {
-            uint8_t hdr[kMaxLengthPrefix];
+            uint8_t hdr[kMaxLengthPrefix] = {};
             const unsigned h = write_length_prefix(bytes, hdr);
-            r = accept_original(element, num, h, bytes);
+            const uint64_t from = src + (uint64_t)k * srcStride;
+
+            // The uniform path: this original and those behind it of the
+            // same length that are not in the window yet, as far as the
+            // subwindow and the call go (packet numbers that wrap, and
+            // anything present, end the run: they go one by one)
+            const unsigned bit = element % kSubwindow;
+            unsigned m = std::min(std::min(count - k, kSubwindow - bit), kColumnPeriod - num);
+            if (lens)
+                for (unsigned j = 1; j < m; ++j)
+                    if (lens[k + j] != bytes) {
+                        m = j;
+                        break;
+                    }
+            DecSubwindow* sw = subwindows_[element / kSubwindow].get();
+            for (unsigned j = 1; j < m; ++j)
+                if ((sw->got >> (bit + j) & 1u) || peek_bytes(element + j) > 0) {
+                    m = j;
+                    break;
+                }
+            if (!(sw->got >> bit & 1u) && uniform_takes(sw, element, m, h + bytes, h, num)) {
+                bool failed = false;
+                const DevBuf b = eng_->slab_slot(sw->slab, bit, h + bytes, &failed);
+                if (failed) {
+                    disabled_ = true;
+                    r = Siamese_Disabled;
+                } else if (b) {
+                    grow_window(element + m);
+                    add_uniform(sw, element, m, h + bytes, h, bytes, num);
+                    append(b.addr(), b.cap, from, bytes, h, hdr, m);
+                    if (results)
+                        for (unsigned j = 0; j < m; ++j)
+                            results[k + j] = Siamese_Success;
+                    k += m;
+                    *added += m;
+                    continue;
+                }
+            }
             if (r == Siamese_Success) {
-                const DecSlot& s = slot(element);
-                const uint64_t from = src + (uint64_t)k * srcStride;
-                if (run.n && run.bytes == bytes && run.n < kIngestRunMax && s.buf.cap == run.stride &&
-                    s.buf.addr() == run.dst + (uint64_t)run.n * run.stride &&
-                    from == run.src + (uint64_t)run.n * srcStride)
-                    ++run.n;
-                else {
-                    close_run();
-                    run.dst = s.buf.addr();
-                    run.src = from;
-                    run.stride = s.buf.cap;
-                    run.n = 1;
-                    run.bytes = bytes;
-                    run.h = h;
-                    std::memcpy(run.hdr, hdr, sizeof(hdr));
+                r = accept_original(element, num, h, bytes);
+                if (r == Siamese_Success) {
+                    const DecSlot& s = slot(element);
+                    append(s.buf.addr(), s.buf.cap, from, bytes, h, hdr, 1);
                 }
             }
         }
         if (results)
             results[k] = r;
         ++*added;
+        ++k;
         if (r != Siamese_Success && r != Siamese_DuplicateData) {
             res = r;
             break;
@@ -514,7 +749,22 @@ void DecoderCore::cover(unsigned lo, unsigned hi)
     uint32_t from = hi;
     WinEntry* w = prog_.rows_window(lo, hi, &from);
     for (unsigned e = from; e < hi; ++e, ++w) {
-        const DecSlot& o = slot(e);
+        const DecSubwindow* sw = subwindows_[e / kSubwindow].get();
+        const unsigned bit = e % kSubwindow;
+        if (sw->uni.mask) {
+            // a uniform subwindow: received originals from the descriptor,
+            // the others are lost (fresh records)
+#ifdef SGPU_SLOT_CHECK
+            if (bit == 0 || e == from)
+                slot_check(sw, "cover");
+#endif
+            const bool in = sw->uni.mask >> bit & 1u;
+            w->src = in ? (uint64_t)(uintptr_t)sw->slab.buf.ptr + (uint64_t)bit * sw->slab.stride : 0;
+            w->len = in ? sw->uni.bytes : 0;
+            w->column = in ? column_add(sw->uni.first, bit) : 0;
+            continue;
+        }
+        const DecSlot& o = sw->slot[bit];
         // lost originals read as absent (their `column` is a matrix column)
         w->src = o.bytes ? o.buf.addr() : 0;
         w->len = o.bytes;
@@ -557,7 +807,7 @@ DevSum& DecoderCore::get_sum(unsigned lane, unsigned s, unsigned elementEnd)
     if (!(ls.from == element && ls.to == elementEnd && ls.epoch == scanEpoch_)) {
         unsigned most = 0, cnt = 0;
         for (; end < elementEnd; end += kLanes) {
-            const unsigned b = slot(end).bytes;
+            const unsigned b = peek_bytes(end);
             if (b > 0) {
                 most = std::max(most, b);
                 ++cnt;
@@ -757,11 +1007,20 @@ void DecoderCore::remove_elements()
         // (slab slots go with the slab, back to the arena after the flushes
         // that read them; owned buffers stay until their slot is reused)
         DecSubwindow* sw = subwindows_[i].get();
-        for (DecSlot& d : sw->slot)
-            if (d.inSlab) {
-                d.buf = DevBuf();
-                d.inSlab = false;
-            }
+        if (sw->uni.mask) {
+#ifdef SGPU_SLOT_CHECK
+            slot_check(sw, "release");
+            for (DecSlot& d : sw->shadow)
+                d = DecSlot();
+#endif
+            sw->uni = DecUniform();
+        } else if (!sw->clean) {
+            for (DecSlot& d : sw->slot)
+                if (d.inSlab) {
+                    d.buf = DevBuf();
+                    d.inSlab = false;
+                }
+        }
         eng_->slab_release(sw->slab);
         sw->reset();
     }
@@ -790,6 +1049,7 @@ void DecoderCore::remove_elements()
 
 void DecSubwindowRecycle::operator()(DecSubwindow* w) const
 {
+    w->uni = DecUniform();
     if (!w->clean) {
         w->got = 0;
         w->gotCount = 0;
@@ -1934,6 +2194,10 @@ void DecoderCore::populate_columns(unsigned oldColumns, unsigned newColumns)
     while (sub < subEnd) {
         DecSubwindow* sw = subwindows_[sub].get();
         if (sw->gotCount < kSubwindow) {
+            // (the lost slots' records become matrix columns)
+            if (sw->uni.mask)
+                demote(sw, kDemoteMatrix);
+            sw->clean = false;
             do {
                 bit = first_clear(sw->got, bit);
                 if (bit >= kSubwindow)
@@ -2682,7 +2946,7 @@ SiameseResult DecoderCore::get(SiameseOriginalPacket& packet)
     if (dead())
         return Siamese_Disabled;
     const unsigned element = column_to_element(packet.PacketNum);
-    if (element >= count_ || slot(element).bytes == 0) {
+    if (element >= count_ || peek_bytes(element) == 0) {
         packet.Data = nullptr;
         packet.DataBytes = 0;
         return Siamese_NeedMoreData;
@@ -2719,6 +2983,17 @@ SiameseResult DecoderCore::get_range(unsigned firstNum, unsigned count, SiameseO
         SiameseOriginalPacket& p = out[k];
         p.PacketNum = (firstNum + k) & SIAMESE_PACKET_NUM_MAX;
         if (ok && e < count_) {
+            const DecSubwindow* sw = subwindows_[e / kSubwindow].get();
+            if (sw->uni.mask >> (e % kSubwindow) & 1u) {
+                // a received original of a uniform subwindow: from the descriptor
+#ifdef SGPU_SLOT_CHECK
+                slot_check(sw, "get_range");
+#endif
+                p.Data = sw->slab.buf.ptr + (size_t)(e % kSubwindow) * sw->slab.stride + sw->uni.header;
+                p.DataBytes = sw->uni.bytes - sw->uni.header;
+                ++*got;
+                continue;
+            }
             DecSlot& s = slot(e);
             if (s.bytes != 0 && !s.pending) {
                 p.Data = (mirror_ ? s.host().data() : s.buf.ptr) + s.header;
@@ -2937,6 +3212,8 @@ SiameseResult DecoderCore::stats(uint64_t* out, unsigned count)
     uint64_t mem = 0;
     for (auto& sw : subwindows_) {
         mem += sw->slab.buf.cap;
+        if (sw->clean)
+            continue;   // (no record written: no slot owns a buffer)
         for (DecSlot& s : sw->slot)
             if (!s.inSlab)
                 mem += s.buf.cap;

@@ -56,17 +56,38 @@ struct DecSlot
     }
 };
 
+/// The decoder's form of EncUniform (encoder.h): the received originals of
+/// `mask` came from range adds of one length and their slot records are not
+/// written.  Slot i has buf = {slab.buf.ptr + i * slab.stride, slab.stride},
+/// inSlab, the shared bytes and header, column first + i, not pending.  Slots
+/// outside the mask (lost so far) are fresh.
+struct DecUniform
+{
+    uint64_t mask = 0;          // slots described, a subset of `got` (0: not uniform)
+    unsigned bytes = 0;
+    unsigned header = 0;
+    unsigned first = 0;         // column of slot 0
+};
+
 struct DecSubwindow
 {
     DecSlot slot[kSubwindow];
     uint64_t got = 0;           // CustomBitSet<64> (PacketAllocator.h:189-437)
     unsigned gotCount = 0;
     Slab slab;                  // the received originals' shared buffer (engine.h)
-    bool clean = false;         // every slot already in its fresh state (the owner's teardown)
+    // every slot in its fresh state: from the pool until a slot record is
+    // written (DecoderCore::slot, place), and again after the owner's teardown
+    bool clean = false;
+    DecUniform uni;
+#ifdef SGPU_SLOT_CHECK
+    DecSlot shadow[kSubwindow];   // (test double) the records the per-element code would have written
+#endif
     void reset()
     {
         got = 0;
         gotCount = 0;
+        if (clean)
+            return;   // (no record was written)
         for (DecSlot& s : slot) {
             s.column = 0;
             s.bytes = 0;
@@ -215,7 +236,7 @@ public:
     {
         settle();
         const unsigned e = column_to_element(packetNum);
-        return !dead() && e < count_ && slot(e).bytes > 0;
+        return !dead() && e < count_ && peek_bytes(e) > 0;
     }
     /// Present, but its exact length still being solved on the device (a
     /// get() would flush and wait).
@@ -223,7 +244,7 @@ public:
     {
         settle();
         const unsigned e = column_to_element(packetNum);
-        return !dead() && e < count_ && slot(e).bytes > 0 && slot(e).pending;
+        return !dead() && e < count_ && peek_bytes(e) > 0 && slot(e).pending;
     }
     /// True while a queued solve has not been resolved by a completed flush.
     bool has_pending() const { return pendingSolves_ > 0; }
@@ -232,7 +253,51 @@ public:
 
 private:
     // ---- window (reference DecoderPacketWindow) ----
-    DecSlot& slot(unsigned e) { return subwindows_[e / kSubwindow]->slot[e % kSubwindow]; }
+    /// Why a uniform subwindow's records were written out (slot counters).
+    enum DemoteCause
+    {
+        kDemoteAdd,      // a single add, a duplicate, or a range add the fast path does not take
+        kDemoteLength,   // a range add of another length or column sequence
+        kDemoteStride,   // a symbol larger than the slab's slots
+        kDemoteMatrix,   // a decode takes the lost slots as matrix columns
+        kDemoteOther,    // any other reader or writer of slot records
+        kDemoteCauses
+    };
+    /// The element's slot record, for code that reads or writes records: a
+    /// uniform subwindow is demoted first.
+    DecSlot& slot(unsigned e, DemoteCause cause = kDemoteOther)
+    {
+        DecSubwindow* sw = subwindows_[e / kSubwindow].get();
+        if (sw->uni.mask)
+            demote(sw, cause);
+        sw->clean = false;
+        return sw->slot[e % kSubwindow];
+    }
+    /// An element's length as its record would say it (never demotes).
+    unsigned peek_bytes(unsigned e) const
+    {
+        const DecSubwindow& sw = *subwindows_[e / kSubwindow];
+        return (sw.uni.mask >> (e % kSubwindow) & 1u) ? sw.uni.bytes : sw.slot[e % kSubwindow].bytes;
+    }
+    static uint64_t run_bits(unsigned bit, unsigned m) { return (m >= 64 ? ~0ull : (1ull << m) - 1) << bit; }
+    /// Write the records of a uniform subwindow's slots from its descriptor:
+    /// afterwards it is what the per-element code would have built.
+    void demote(DecSubwindow* sw, DemoteCause cause);
+    /// add_original_range: may the m originals of `need` bytes from `element`
+    /// on (one subwindow's, none received yet, the first with `column`) be
+    /// added through the descriptor?  A uniform subwindow they do not continue
+    /// is demoted here.
+    bool uniform_takes(DecSubwindow* sw, unsigned element, unsigned m, unsigned need, unsigned h, unsigned column);
+    /// ... then, the first's slab slot taken: the descriptor and, in bulk, what
+    /// accept_original does for each of them.
+    void add_uniform(DecSubwindow* sw, unsigned element, unsigned m, unsigned need, unsigned h, unsigned bytes,
+                     unsigned column);
+#ifdef SGPU_SLOT_CHECK
+    void slot_check(const DecSubwindow* sw, const char* where) const;
+    [[noreturn]] static void slot_check_failed(const char* where, const char* what, unsigned bit);
+#endif
+    unsigned uniformEntered_ = 0, slotWrites_ = 0;
+    unsigned demotions_[kDemoteCauses] = {};
     unsigned column_to_element(unsigned c) const { return column_sub(c, columnStart_); }
     unsigned element_to_column(unsigned e) const { return column_add(e, columnStart_); }
     unsigned next_lane_element(unsigned element, unsigned lane) const

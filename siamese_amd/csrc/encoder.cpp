@@ -4,9 +4,41 @@
 #include "frames.h"
 
 #include <algorithm>
+#include <atomic>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 namespace sgpu {
+
+namespace {
+
+// Slot bookkeeping of all encoders of the process, printed at exit when
+// SIAMESE_AMD_SLOT_COUNTS is set (read once): subwindows that entered the
+// uniform state, demotions by cause, slot records written (by the
+// per-element code and by demotions).  Each encoder counts for itself and
+// adds its counts here when it is freed.
+constexpr unsigned kSlotCauses = 6;
+const char* const kSlotCauseNames[kSlotCauses] = {"add", "length", "stride", "stamp", "arq", "other"};
+struct SlotCounts
+{
+    const bool on = std::getenv("SIAMESE_AMD_SLOT_COUNTS") != nullptr;
+    std::atomic<uint64_t> encoders{0}, uniform{0}, writes{0};
+    std::atomic<uint64_t> demote[kSlotCauses] = {};
+    ~SlotCounts()
+    {
+        if (!on)
+            return;
+        std::fprintf(stderr, "slot counts: encoders %llu enc_uniform %llu enc_slot_writes %llu",
+                     (unsigned long long)encoders.load(), (unsigned long long)uniform.load(),
+                     (unsigned long long)writes.load());
+        for (unsigned c = 0; c < kSlotCauses; ++c)
+            std::fprintf(stderr, " enc_demote_%s %llu", kSlotCauseNames[c], (unsigned long long)demote[c].load());
+        std::fprintf(stderr, "\n");
+    }
+} g_slots;
+
+} // namespace
 
 EncoderCore::EncoderCore(Engine* eng, bool hostMirror) : eng_(eng), prog_(eng, 0), mirror_(hostMirror)
 {
@@ -27,20 +59,38 @@ EncoderCore::~EncoderCore()
 {
     // one pass per subwindow: release owned buffers and leave the slots
     // fresh for the pool (EncSubwindowRecycle skips a clean subwindow)
+    // (a uniform subwindow, or one never written, has fresh slots already)
     for (auto& sw : subwindows_) {
-        for (EncSlot& s : sw->slot) {
-            if (!s.inSlab)
-                eng_->release(s.buf);
-            s.buf = DevBuf();
-            s.inSlab = false;
-            s.bytes = s.column = s.header = 0;
-            s.lastSend = 0;
-            if (s.hostp)
-                s.hostp->clear();
+        if (sw->uni.mask) {
+#ifdef SGPU_SLOT_CHECK
+            slot_check(sw.get(), "teardown");
+            for (EncSlot& s : sw->shadow)
+                s = EncSlot();
+#endif
+            sw->uni = EncUniform();
         }
+        if (!sw->clean)
+            for (EncSlot& s : sw->slot) {
+                if (!s.inSlab)
+                    eng_->release(s.buf);
+                s.buf = DevBuf();
+                s.inSlab = false;
+                s.bytes = s.column = s.header = 0;
+                s.lastSend = 0;
+                if (s.hostp)
+                    s.hostp->clear();
+            }
         eng_->slab_release(sw->slab);
         sw->slab = Slab();
         sw->clean = true;
+    }
+    static_assert(kDemoteCauses == kSlotCauses, "a name for every cause");
+    if (g_slots.on) {
+        g_slots.encoders.fetch_add(1, std::memory_order_relaxed);
+        g_slots.uniform.fetch_add(uniformEntered_, std::memory_order_relaxed);
+        g_slots.writes.fetch_add(slotWrites_, std::memory_order_relaxed);
+        for (unsigned c = 0; c < kSlotCauses; ++c)
+            g_slots.demote[c].fetch_add(demotions_[c], std::memory_order_relaxed);
     }
     for (Lane& l : lanes_)
         for (DevSum& s : l.sum)
@@ -68,7 +118,7 @@ unsigned EncoderCore::take_element()
     // Keep one lane-width of spare slots ahead of the last subwindow (:108-118)
     if (element + kLanes >= subwindows_.size() * kSubwindow) {
         subwindows_.emplace_back(ObjPool<EncSubwindow>::get());
-        subwindows_.back()->clean = false;
+        subwindows_.back()->clean = true;   // (the pool's objects are fresh)
     }
 
     if (count_ > 0)
@@ -80,9 +130,106 @@ unsigned EncoderCore::take_element()
     return element;
 }
 
+void EncoderCore::demote(EncSubwindow* sw, DemoteCause cause)
+{
+#ifdef SGPU_SLOT_CHECK
+    slot_check(sw, "demote");
+    for (EncSlot& s : sw->shadow)
+        s = EncSlot();
+#endif
+    const EncUniform u = sw->uni;
+    for (uint64_t m = u.mask; m; m &= m - 1) {
+        const unsigned bit = (unsigned)__builtin_ctzll(m);
+        EncSlot& s = sw->slot[bit];
+        s.buf.ptr = sw->slab.buf.ptr + (size_t)bit * sw->slab.stride;
+        s.buf.cap = sw->slab.stride;
+        s.inSlab = true;
+        s.bytes = u.bytes;
+        s.header = u.header;
+        s.column = column_add(u.first, bit);
+        s.lastSend = u.stamp;
+    }
+    sw->uni = EncUniform();
+    sw->clean = false;
+    slotWrites_ += (unsigned)__builtin_popcountll(u.mask);
+    ++demotions_[cause];
+}
+
+void EncoderCore::release_subwindow(EncSubwindow* sw)
+{
+    if (sw->uni.mask) {
+#ifdef SGPU_SLOT_CHECK
+        slot_check(sw, "release");
+        for (EncSlot& s : sw->shadow)
+            s = EncSlot();
+#endif
+        sw->uni = EncUniform();
+    } else if (!sw->clean) {
+        // (its records keep their lengths and columns, as they always have,
+        // and `clean` stays false: a subwindow that was demoted or filled
+        // element by element is per-element until the encoder is freed.
+        // Intended: making it fresh again would cost this walk 64 more
+        // record writes for a case the headline never meets.)
+        for (EncSlot& s : sw->slot)
+            if (s.inSlab) {
+                s.buf = DevBuf();
+                s.inSlab = false;
+            }
+    }
+    eng_->slab_release(sw->slab);
+}
+
+#ifdef SGPU_SLOT_CHECK
+void EncoderCore::slot_check_failed(const char* where, const char* what, unsigned bit)
+{
+    std::fprintf(stderr, "SGPU_SLOT_CHECK: encoder %s: slot %u: %s differs from the per-element record\n", where, bit,
+                 what);
+    std::abort();
+}
+
+void EncoderCore::slot_check(const EncSubwindow* sw, const char* where) const
+{
+    const EncUniform& u = sw->uni;
+    if (!sw->clean)
+        slot_check_failed(where, "clean", 0);
+    for (unsigned bit = 0; bit < kSubwindow; ++bit) {
+        const EncSlot& sh = sw->shadow[bit];
+        const EncSlot& real = sw->slot[bit];
+        if (real.buf.ptr || real.buf.cap || real.inSlab || real.bytes || real.column || real.header ||
+            real.lastSend)
+            slot_check_failed(where, "fresh slot[]", bit);
+        if (!(u.mask >> bit & 1u)) {
+            if (sh.buf.ptr || sh.bytes || sh.inSlab)
+                slot_check_failed(where, "mask", bit);
+            continue;
+        }
+        if (sh.buf.ptr != sw->slab.buf.ptr + (size_t)bit * sw->slab.stride)
+            slot_check_failed(where, "buf.ptr", bit);
+        if (sh.buf.cap != sw->slab.stride)
+            slot_check_failed(where, "buf.cap", bit);
+        if (!sh.inSlab)
+            slot_check_failed(where, "inSlab", bit);
+        if (!(sw->slab.used >> bit & 1u))
+            slot_check_failed(where, "slab.used", bit);
+        if (sh.bytes != u.bytes)
+            slot_check_failed(where, "bytes", bit);
+        if (sh.header != u.header)
+            slot_check_failed(where, "header", bit);
+        if (sh.column != column_add(u.first, bit))
+            slot_check_failed(where, "column", bit);
+        if (sh.lastSend != u.stamp)
+            slot_check_failed(where, "lastSend", bit);
+    }
+}
+#endif
+
 bool EncoderCore::place(unsigned element, unsigned need)
 {
     EncSubwindow* sw = subwindows_[element / kSubwindow].get();
+    if (sw->uni.mask)
+        demote(sw, kDemoteAdd);
+    sw->clean = false;
+    ++slotWrites_;
     EncSlot& s = sw->slot[element % kSubwindow];
     release_slot(s);
     bool failed = false;
@@ -147,6 +294,125 @@ SiameseResult EncoderCore::add(SiameseOriginalPacket& packet, uint64_t deviceSrc
     return Siamese_Success;
 }
 
+bool EncoderCore::uniform_takes(EncSubwindow* sw, unsigned element, unsigned m, unsigned need, unsigned h,
+                                unsigned column, uint32_t stamp)
+{
+    if (mirror_ || !sw->clean)
+        return false;
+    const unsigned bit = element % kSubwindow;
+    const EncUniform& u = sw->uni;
+    if (!u.mask)   // fresh: no slab yet, and one that slab_slot will grant
+        return !sw->slab.buf && slab_stride(need) != 0;
+    // (one cause per demotion, the first that applies)
+    if (need > sw->slab.stride)
+        demote(sw, kDemoteStride);
+    else if (u.bytes != need || u.header != h || column_add(u.first, bit) != column)
+        demote(sw, kDemoteLength);
+    else if (u.stamp != stamp)
+        demote(sw, kDemoteStamp);
+    else if (sw->slab.used & run_bits(bit, m))
+        demote(sw, kDemoteAdd);
+    else
+        return true;
+    return false;
+}
+
+void EncoderCore::add_uniform(EncSubwindow* sw, unsigned element, unsigned m, unsigned need, unsigned h,
+                              unsigned bytes, unsigned column, uint32_t stamp)
+{
+    const unsigned bit = element % kSubwindow;
+    const uint64_t bits = run_bits(bit, m);
+    sw->slab.used |= bits;
+    if (!sw->uni.mask) {
+        sw->uni.bytes = need;
+        sw->uni.header = h;
+        sw->uni.first = column_sub(column, bit);
+        sw->uni.stamp = stamp;
+        ++uniformEntered_;
+    }
+    sw->uni.mask |= bits;
+    // what fill_slot and take_element do for each of the m
+    nextColumn_ = column_add(nextColumn_, m);
+    for (unsigned j = 0; j < std::min(m, kLanes); ++j) {
+        const unsigned l = (column + j) % kLanes;
+        staleSums_ |= 7u << (l * kSums);
+        if (lanes_[l].longest < need)
+            lanes_[l].longest = need;
+    }
+    if (longest_ < need)
+        longest_ = need;
+    stats_[SiameseEncoderStats_OriginalCount] += m;
+    stats_[SiameseEncoderStats_OriginalBytes] += (uint64_t)m * bytes;
+    count_ += m - 1;
+    // (take_element's growth rule: of the elements behind the first, only
+    // the subwindow's last ones can ask for another, and for one only)
+    if (m > 1 && element + m - 1 + kLanes >= subwindows_.size() * kSubwindow) {
+        subwindows_.emplace_back(ObjPool<EncSubwindow>::get());
+        subwindows_.back()->clean = true;
+    }
+}
+
+#ifdef SGPU_SLOT_CHECK
+EncoderCore::AddExpect EncoderCore::slot_check_add(EncSubwindow* sw, unsigned element, unsigned m, const unsigned* lens,
+                                                   unsigned fixedBytes, uint32_t stamp)
+{
+    // the per-element code on a copy of the window's lengths and counters
+    // (the first element's take_element has run), its records into the shadow
+    AddExpect x;
+    x.nextColumn = nextColumn_;
+    x.stale = staleSums_;
+    x.longest = longest_;
+    for (unsigned l = 0; l < kLanes; ++l)
+        x.laneLongest[l] = lanes_[l].longest;
+    x.oc = stats_[SiameseEncoderStats_OriginalCount];
+    x.ob = stats_[SiameseEncoderStats_OriginalBytes];
+    x.count = count_;
+    x.subs = subwindows_.size();
+    const unsigned bit = element % kSubwindow;
+    for (unsigned j = 0; j < m; ++j) {
+        const unsigned len = lens ? lens[j] : fixedBytes;
+        uint8_t hd[kMaxLengthPrefix];
+        const unsigned hj = write_length_prefix(len, hd);
+        const unsigned cj = x.nextColumn;
+        if (j > 0) {
+            if (x.count + kLanes >= x.subs * kSubwindow)
+                ++x.subs;
+            ++x.count;
+        }
+        EncSlot& sh = sw->shadow[bit + j];
+        if (sh.buf.ptr || sh.bytes)
+            slot_check_failed("add_range", "slot written before", bit + j);
+        sh.buf.ptr = sw->slab.buf.ptr + (size_t)(bit + j) * sw->slab.stride;
+        sh.buf.cap = sw->slab.stride;
+        sh.inSlab = true;
+        sh.header = hj;
+        sh.bytes = hj + len;
+        sh.column = cj;
+        sh.lastSend = stamp;
+        x.nextColumn = column_add(x.nextColumn, 1);
+        x.stale |= 7u << (cj % kLanes * kSums);
+        x.laneLongest[cj % kLanes] = std::max(x.laneLongest[cj % kLanes], sh.bytes);
+        x.longest = std::max(x.longest, sh.bytes);
+        ++x.oc;
+        x.ob += len;
+        if ((element + j) % kLanes != cj % kLanes)
+            slot_check_failed("add_range", "element % 8 == column % 8", bit + j);
+    }
+    return x;
+}
+
+void EncoderCore::slot_check_added(const AddExpect& x) const
+{
+    if (x.nextColumn != nextColumn_ || x.stale != staleSums_ || x.longest != longest_ ||
+        x.oc != stats_[SiameseEncoderStats_OriginalCount] || x.ob != stats_[SiameseEncoderStats_OriginalBytes] ||
+        x.count != count_ || x.subs != subwindows_.size())
+        slot_check_failed("add_range", "window bookkeeping", 0);
+    for (unsigned l = 0; l < kLanes; ++l)
+        if (x.laneLongest[l] != lanes_[l].longest)
+            slot_check_failed("add_range", "lane longest", l);
+}
+#endif
+
 SiameseResult EncoderCore::add_range(uint64_t src, uint32_t srcStride, const unsigned* lens, unsigned fixedBytes,
                                      unsigned count, unsigned* firstNum, unsigned* added)
 {
@@ -168,8 +434,30 @@ SiameseResult EncoderCore::add_range(uint64_t src, uint32_t srcStride, const uns
             prog_.ingest_run(run.dst, run.stride, run.src, srcStride, run.n, run.bytes, run.hdr, run.h);
         run.n = 0;
     };
+    // `n` symbols of one length into consecutive slots of `cap` bytes from
+    // dst: the runs the per-element code makes of them (<= kIngestRunMax each)
+    auto append = [&](uint64_t dst, uint32_t cap, uint64_t from, unsigned bytes, unsigned h, const uint8_t* hdr,
+                      unsigned n) {
+        while (n) {
+            if (!(run.n && run.bytes == bytes && run.n < kIngestRunMax && cap == run.stride &&
+                  dst == run.dst + (uint64_t)run.n * run.stride && from == run.src + (uint64_t)run.n * srcStride)) {
+                close_run();
+                run.dst = dst;
+                run.src = from;
+                run.stride = cap;
+                run.bytes = bytes;
+                run.h = h;
+                std::memcpy(run.hdr, hdr, kMaxLengthPrefix);
+            }
+            const unsigned t = std::min<unsigned>(n, kIngestRunMax - run.n);
+            run.n += t;
+            dst += (uint64_t)t * cap;
+            from += (uint64_t)t * srcStride;
+            n -= t;
+        }
+    };
     SiameseResult res = Siamese_Success;
-    for (unsigned k = 0; k < count; ++k) {
+    for (unsigned k = 0; k < count;) {
         const unsigned bytes = lens ? lens[k] : fixedBytes;
         if (bytes == 0 || bytes > SIAMESE_MAX_PACKET_BYTES) {
             res = Siamese_InvalidInput;
@@ -181,30 +469,54 @@ SiameseResult EncoderCore::add_range(uint64_t src, uint32_t srcStride, const uns
         }
         const unsigned column = nextColumn_;
         const unsigned element = take_element();
-        uint8_t hdr[kMaxLengthPrefix];
+        uint8_t hdr[kMaxLengthPrefix] = {};
         const unsigned h = write_length_prefix(bytes, hdr);
-        if (!place(element, h + bytes)) {
+        const unsigned need = h + bytes;
+        const uint64_t from = src + (uint64_t)k * srcStride;
+
+        // The uniform path: this original and those behind it of the same
+        // length, as far as the subwindow, the window's limit and the call go
+        EncSubwindow* sw = subwindows_[element / kSubwindow].get();
+        unsigned m = std::min(std::min(count - k, kSubwindow - element % kSubwindow), 1 + remaining_slots());
+        if (lens)
+            for (unsigned j = 1; j < m; ++j)
+                if (lens[k + j] != bytes) {
+                    m = j;
+                    break;
+                }
+        if (uniform_takes(sw, element, m, need, h, column, stamp)) {
+            bool failed = false;
+            const DevBuf b = eng_->slab_slot(sw->slab, element % kSubwindow, need, &failed);
+            if (failed) {
+                disabled_ = true;
+                res = Siamese_Disabled;
+                break;
+            }
+            if (b) {
+#ifdef SGPU_SLOT_CHECK
+                const AddExpect expect = slot_check_add(sw, element, m, lens ? lens + k : nullptr, fixedBytes, stamp);
+#endif
+                add_uniform(sw, element, m, need, h, bytes, column, stamp);
+#ifdef SGPU_SLOT_CHECK
+                slot_check_added(expect);
+#endif
+                append(b.addr(), b.cap, from, bytes, h, hdr, m);
+                k += m;
+                *added += m;
+                continue;
+            }
+        }
+
+        // one element as add() places it
+        if (!place(element, need)) {
             res = Siamese_Disabled;
             break;
         }
         EncSlot& s = slot(element);
-        const uint64_t from = src + (uint64_t)k * srcStride;
-        if (run.n && run.bytes == bytes && run.n < kIngestRunMax && s.buf.cap == run.stride &&
-            s.buf.addr() == run.dst + (uint64_t)run.n * run.stride &&
-            from == run.src + (uint64_t)run.n * srcStride)
-            ++run.n;
-        else {
-            close_run();
-            run.dst = s.buf.addr();
-            run.src = from;
-            run.stride = s.buf.cap;
-            run.n = 1;
-            run.bytes = bytes;
-            run.h = h;
-            std::memcpy(run.hdr, hdr, sizeof(hdr));
-        }
+        append(s.buf.addr(), s.buf.cap, from, bytes, h, hdr, 1);
         fill_slot(s, column, h, bytes, stamp);
         ++*added;
+        ++k;
     }
     close_run();
     return res;
@@ -215,14 +527,8 @@ void EncoderCore::start_window(unsigned column)
     // :163-181 -- element % 8 == column % 8 is an invariant of the window
     const unsigned element = column % kLanes;
     // every element of the old window was acknowledged: slabs start afresh
-    for (auto& sw : subwindows_) {
-        for (EncSlot& s : sw->slot)
-            if (s.inSlab) {
-                s.buf = DevBuf();
-                s.inSlab = false;
-            }
-        eng_->slab_release(sw->slab);
-    }
+    for (auto& sw : subwindows_)
+        release_subwindow(sw.get());
     columnStart_ = column - element;
     sumStart_ = element;
     sumEnd_ = element;
@@ -293,15 +599,8 @@ void EncoderCore::remove_elements()
     prog_.rows_seal();
     // Removed subwindows rotate to the back for reuse; their slabs go back
     // to the arena (after the flushes that read them)
-    for (unsigned i = 0; i < keptSub; ++i) {
-        EncSubwindow* sw = subwindows_[i].get();
-        for (EncSlot& s : sw->slot)
-            if (s.inSlab) {
-                s.buf = DevBuf();
-                s.inSlab = false;
-            }
-        eng_->slab_release(sw->slab);
-    }
+    for (unsigned i = 0; i < keptSub; ++i)
+        release_subwindow(subwindows_[i].get());
     std::rotate(subwindows_.begin(), subwindows_.begin() + keptSub, subwindows_.end());
 
     count_ -= removed;
@@ -313,7 +612,7 @@ void EncoderCore::remove_elements()
     unsigned longest = 0;
     unsigned laneLongest[kLanes] = {0};
     for (unsigned e = firstUnremoved_; e < count_; ++e) {
-        const unsigned b = slot(e).bytes;
+        const unsigned b = peek(e).bytes;
         longest = std::max(longest, b);
         laneLongest[e % kLanes] = std::max(laneLongest[e % kLanes], b);
     }
@@ -351,11 +650,33 @@ void EncoderCore::cover(unsigned lo, unsigned hi)
 {
     uint32_t from = hi;
     WinEntry* w = prog_.rows_window(lo, hi, &from);
-    for (unsigned e = from; e < hi; ++e, ++w) {
-        const EncSlot& o = slot(e);
-        w->src = o.buf.addr();
-        w->len = o.bytes;
-        w->column = o.column;
+    for (unsigned e = from; e < hi;) {
+        // one subwindow's part of the snapshot: from its descriptor when
+        // that describes all of it, else element by element
+        const EncSubwindow* sw = subwindows_[e / kSubwindow].get();
+        const unsigned bit = e % kSubwindow;
+        const unsigned n = std::min(hi - e, kSubwindow - bit);
+        const uint64_t bits = (n == kSubwindow ? ~0ull : (1ull << n) - 1) << bit;
+#ifdef SGPU_SLOT_CHECK
+        if (sw->uni.mask)
+            slot_check(sw, "cover");
+#endif
+        if ((sw->uni.mask & bits) == bits) {
+            uint64_t at = (uint64_t)(uintptr_t)sw->slab.buf.ptr + (uint64_t)bit * sw->slab.stride;
+            for (unsigned j = 0; j < n; ++j, ++w, at += sw->slab.stride) {
+                w->src = at;
+                w->len = sw->uni.bytes;
+                w->column = column_add(sw->uni.first, bit + j);
+            }
+        } else {
+            for (unsigned j = 0; j < n; ++j, ++w) {
+                const SlotView o = peek(e + j);
+                w->src = o.addr();
+                w->len = o.bytes;
+                w->column = o.column;
+            }
+        }
+        e += n;
     }
 }
 
@@ -376,7 +697,7 @@ DevSum& EncoderCore::get_sum(unsigned lane, unsigned sumIndex, unsigned elementE
     unsigned newBytes = std::max(sum.bytes, L.longest);
     const unsigned end = element + ((elementEnd - element + kLanes - 1) / kLanes) * kLanes;
     for (unsigned e = element; e < end && e < firstUnremoved_; e += kLanes)
-        newBytes = std::max(newBytes, slot(e).bytes);
+        newBytes = std::max(newBytes, peek(e).bytes);
     if (!grow_sum(sum, newBytes))
         return sum;
     // reference source bytes (one add/muladd per original) are counted by
@@ -394,7 +715,7 @@ SiameseResult EncoderCore::get(SiameseOriginalPacket& packet)
     if (dead())
         return Siamese_Disabled;
     const unsigned element = column_to_element(packet.PacketNum);
-    if (element >= count_ || slot(element).bytes == 0) {
+    if (element >= count_ || peek(element).bytes == 0) {
         packet.Data = nullptr;
         packet.DataBytes = 0;
         return Siamese_NeedMoreData;
@@ -418,7 +739,7 @@ SiameseResult EncoderCore::deliver_range(unsigned firstNum, unsigned count, unsi
         const unsigned e = column_to_element(column);
         if (e >= count_ || e < firstUnremoved_)
             return nullptr;
-        const EncSlot& s = slot(e);
+        const EncSlot& s = slot(e);   // (demotes: delivery reads records)
         return s.bytes != 0 && s.column == column ? &s : nullptr;
     };
     // every length is known here: nothing is queued when a packet cannot fit
@@ -546,7 +867,7 @@ SiameseResult EncoderCore::retransmit_frames(unsigned flow, unsigned maxPackets,
     // the longest frame a retransmission of the current window can need
     uint64_t worst = 0;
     for (unsigned e = firstUnremoved_; e < count_; ++e) {
-        const EncSlot& s = slot(e);
+        const SlotView s = peek(e);
         if (s.bytes > s.header) {
             const unsigned n = s.bytes - s.header;
             worst = std::max<uint64_t>(worst, (uint64_t)frame_header_bytes(kFrameOriginal, n) + n);
@@ -745,11 +1066,11 @@ SiameseResult EncoderCore::encode_range_more(EncodeOut* out, unsigned count, uns
 SiameseResult EncoderCore::single_row(EncodeOut& out)
 {
     // :1296-1329 -- the lone original itself, with a SumCount=1 footer
-    const EncSlot& o = slot(firstUnremoved_);
+    const SlotView o = peek(firstUnremoved_);
     if (!ensure_recovery(o.bytes + kMaxFooterBytes))
         return Siamese_Disabled;
     prog_.lc_begin(recovery_.addr(), o.bytes, 0);
-    prog_.lc_term(o.buf.addr(), o.bytes, 1);
+    prog_.lc_term(o.addr(), o.bytes, 1);
     prog_.lc_end();
     write_length_prefix(o.bytes - o.header, out.head);
     RowMeta m;
@@ -775,7 +1096,7 @@ SiameseResult EncoderCore::cauchy_row(EncodeOut& out)
 
     unsigned used = 0;
     for (unsigned e = first; e < count_; ++e)
-        used = std::max(used, slot(e).bytes);
+        used = std::max(used, peek(e).bytes);
     prog_.lc_begin(recovery_.addr(), used, 0);
     uint64_t opBytes = 0;
 
@@ -784,8 +1105,8 @@ SiameseResult EncoderCore::cauchy_row(EncodeOut& out)
         nextParityColumn_ = column_add(m.columnStart, inFlight);
         m.row = 0;
         for (unsigned e = first; e < count_; ++e) {
-            const EncSlot& o = slot(e);
-            prog_.lc_term(o.buf.addr(), o.bytes, 1);
+            const SlotView o = peek(e);
+            prog_.lc_term(o.addr(), o.bytes, 1);
             // the reference memcpy's the first parity column (no GF op)
             if (e > first)
                 opBytes += o.bytes;
@@ -797,8 +1118,8 @@ SiameseResult EncoderCore::cauchy_row(EncodeOut& out)
             nextCauchyRow_ = 0;
         unsigned ccol = m.columnStart % kCauchyMaxColumns;
         for (unsigned e = first; e < count_; ++e) {
-            const EncSlot& o = slot(e);
-            prog_.lc_term(o.buf.addr(), o.bytes, cauchy_element(crow, ccol));
+            const SlotView o = peek(e);
+            prog_.lc_term(o.addr(), o.bytes, cauchy_element(crow, ccol));
             opBytes += o.bytes;
             ccol = (ccol + 1) % kCauchyMaxColumns;
         }
@@ -903,6 +1224,8 @@ SiameseResult EncoderCore::stats(uint64_t* out, unsigned count)
     uint64_t mem = recovery_.cap;
     for (auto& sw : subwindows_) {
         mem += sw->slab.buf.cap;
+        if (sw->clean)
+            continue;   // (no record written: no slot owns a buffer)
         for (EncSlot& s : sw->slot)
             if (!s.inSlab)
                 mem += s.buf.cap;

@@ -37,11 +37,33 @@ struct EncSlot
     }
 };
 
+/// A subwindow whose originals came from range adds of one length says in one
+/// descriptor what its slot records would say, and leaves them unwritten
+/// ("uniform").  Slot i of `mask` has buf = {slab.buf.ptr + i * slab.stride,
+/// slab.stride}, inSlab, the shared bytes and header, column first + i and
+/// lastSend = stamp.  Slots outside the mask are fresh.
+struct EncUniform
+{
+    uint64_t mask = 0;          // slots described (0: the subwindow is not uniform)
+    unsigned bytes = 0;         // prefix + payload of each
+    unsigned header = 0;
+    unsigned first = 0;         // column of slot 0
+    uint32_t stamp = 0;         // lastSend of each
+};
+
 struct EncSubwindow
 {
     EncSlot slot[kSubwindow];
     Slab slab;                  // the slots' shared buffer (engine.h)
-    bool clean = false;         // every slot already in its fresh state (the owner's teardown)
+    // every slot in its fresh state: from the pool until a slot record is
+    // written (EncoderCore::slot, place), and again after the owner's teardown
+    bool clean = false;
+    EncUniform uni;
+#ifdef SGPU_SLOT_CHECK
+    // (the test double's build) the records the per-element code would have
+    // written for the uniform slots, compared with the descriptor's view
+    EncSlot shadow[kSubwindow];
+#endif
 };
 
 /// unique_ptr deleter: subwindows go back to the thread's pool, emptied
@@ -50,6 +72,7 @@ struct EncSubwindowRecycle
 {
     void operator()(EncSubwindow* w) const
     {
+        w->uni = EncUniform();
         if (!w->clean) {
             w->slab = Slab();
             for (EncSlot& s : w->slot) {
@@ -183,10 +206,90 @@ public:
 
 private:
     // window (reference EncoderPacketWindow)
-    EncSlot& slot(unsigned element)
+    /// Why a uniform subwindow's records were written out (slot counters).
+    enum DemoteCause
     {
-        return subwindows_[element / kSubwindow]->slot[element % kSubwindow];
+        kDemoteAdd,      // a single add, or a range add the fast path does not take
+        kDemoteLength,   // a range add of another length or column sequence
+        kDemoteStride,   // a symbol larger than the slab's slots
+        kDemoteStamp,    // a range add of the same shape at another send time
+        kDemoteArq,      // a retransmission stamps one element
+        kDemoteOther,    // any other reader or writer of slot records
+        kDemoteCauses
+    };
+    /// The element's slot record, for code that reads or writes records: a
+    /// uniform subwindow is demoted first.
+    EncSlot& slot(unsigned element, DemoteCause cause = kDemoteOther)
+    {
+        EncSubwindow* sw = subwindows_[element / kSubwindow].get();
+        if (sw->uni.mask)
+            demote(sw, cause);
+        sw->clean = false;
+        return sw->slot[element % kSubwindow];
     }
+    /// What an element's record says, read from the descriptor where the
+    /// subwindow is uniform (never demotes).
+    struct SlotView
+    {
+        uint8_t* ptr = nullptr;
+        unsigned bytes = 0, column = 0, header = 0;
+        uint32_t lastSend = 0;
+        uint64_t addr() const { return (uint64_t)(uintptr_t)ptr; }
+    };
+    SlotView peek(unsigned element) const
+    {
+        const EncSubwindow& sw = *subwindows_[element / kSubwindow];
+        const unsigned bit = element % kSubwindow;
+        SlotView v;
+        if (sw.uni.mask >> bit & 1u) {
+            v.ptr = sw.slab.buf.ptr + (size_t)bit * sw.slab.stride;
+            v.bytes = sw.uni.bytes;
+            v.column = column_add(sw.uni.first, bit);
+            v.header = sw.uni.header;
+            v.lastSend = sw.uni.stamp;
+        } else {
+            const EncSlot& s = sw.slot[bit];
+            v.ptr = s.buf.ptr;
+            v.bytes = s.bytes;
+            v.column = s.column;
+            v.header = s.header;
+            v.lastSend = s.lastSend;
+        }
+        return v;
+    }
+    /// Write the records of a uniform subwindow's slots from its descriptor:
+    /// afterwards it is what the per-element code would have built.
+    void demote(EncSubwindow* sw, DemoteCause cause);
+    /// Slots [bit, bit + m) of a subwindow as a mask.
+    static uint64_t run_bits(unsigned bit, unsigned m) { return (m >= 64 ? ~0ull : (1ull << m) - 1) << bit; }
+    /// add_range: may the m originals of `need` bytes from `element` on (one
+    /// subwindow's, the first with `column`) be added through the descriptor?
+    /// A uniform subwindow they do not continue is demoted here.
+    bool uniform_takes(EncSubwindow* sw, unsigned element, unsigned m, unsigned need, unsigned h, unsigned column,
+                       uint32_t stamp);
+    /// ... then, the first's slab slot taken: the descriptor and, in bulk,
+    /// what take_element and fill_slot do for each of them.
+    void add_uniform(EncSubwindow* sw, unsigned element, unsigned m, unsigned need, unsigned h, unsigned bytes,
+                     unsigned column, uint32_t stamp);
+    /// The slab of a subwindow leaving the window goes back to the arena; the
+    /// records of slab slots forget their buffers (none when it is uniform).
+    void release_subwindow(EncSubwindow* sw);
+#ifdef SGPU_SLOT_CHECK
+    void slot_check(const EncSubwindow* sw, const char* where) const;
+    /// What the per-element code makes of add_uniform's originals (their
+    /// records go into the shadow), compared after it.
+    struct AddExpect
+    {
+        unsigned nextColumn, longest, laneLongest[kLanes], count;
+        uint32_t stale;
+        uint64_t oc, ob;
+        size_t subs;
+    };
+    AddExpect slot_check_add(EncSubwindow* sw, unsigned element, unsigned m, const unsigned* lens, unsigned fixedBytes,
+                             uint32_t stamp);
+    void slot_check_added(const AddExpect& x) const;
+    [[noreturn]] static void slot_check_failed(const char* where, const char* what, unsigned bit);
+#endif
     unsigned column_to_element(unsigned c) const { return column_sub(c, columnStart_); }
     unsigned element_to_column(unsigned e) const { return column_add(e, columnStart_); }
     unsigned next_lane_element(unsigned element, unsigned lane) const
@@ -277,6 +380,11 @@ private:
     unsigned nextCauchyRow_ = 0;
 
     uint64_t stats_[SiameseEncoderStats_Count] = {};
+
+    // slot counters of this encoder (summed at teardown, printed at exit with
+    // SIAMESE_AMD_SLOT_COUNTS)
+    unsigned uniformEntered_ = 0, slotWrites_ = 0;
+    unsigned demotions_[kDemoteCauses] = {};
 };
 
 } // namespace sgpu

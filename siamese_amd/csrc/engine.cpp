@@ -1234,11 +1234,9 @@ DevBuf Engine::slab_slot(Slab& sl, unsigned bit, uint32_t need, bool* failed)
 {
     *failed = false;
     if (!sl.buf) {
-        // slots of one MTU-sized class at least: a subwindow of small and
-        // mixed-size datagrams still shares one slab
-        constexpr uint32_t kMinSlot = 1408;
-        const uint32_t stride = round_cap(std::max(need, kMinSlot));
-        if ((uint64_t)stride * kSubwindow > 0xffffffffu)
+        static_assert(kSubwindow == 64, "slab_stride's slot count");
+        const uint32_t stride = slab_stride(need);
+        if (!stride)
             return DevBuf();
         sl.buf = alloc(stride * kSubwindow);
         if (!sl.buf) {

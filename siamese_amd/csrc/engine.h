@@ -208,6 +208,18 @@ struct Slab
     uint64_t used = 0;   // slots written since the slab was taken
 };
 
+/// The stride a fresh slab takes for a first symbol of `need` bytes (slots
+/// of one MTU-sized class at least: a subwindow of small and mixed-size
+/// datagrams still shares one slab), or 0 when 64 such slots pass 4 GiB and
+/// the subwindow gets no slab.  Engine::slab_slot's rule, for callers that
+/// decide before they take the slab.
+constexpr uint32_t kSlabMinSlot = 1408;
+inline uint32_t slab_stride(uint32_t need)
+{
+    const uint32_t stride = round_cap(need > kSlabMinSlot ? need : kSlabMinSlot);
+    return (uint64_t)stride * 64 > 0xffffffffu ? 0 : stride;
+}
+
 class Engine;
 struct Shard;
 struct Batch;
