@@ -971,7 +971,15 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// sgpu_frames_scan_duplex, counted as [24], then [28] the ack frames queued
 /// (sgpu_decoders_ack_frames, counted by the call), then [29] the stream items
 /// queued (sgpu_decoder_deliver_stream: one per packet of the range's leading
-/// present run, counted as [26]); count entries at most.
+/// present run, counted as [26]), then the Siamese row batches by the executor
+/// mode their shape selects, counted when their submission is laid out: [30]
+/// the batches, [31] those in which a row reads a lane sum that a later row's
+/// originals were folded into (versioned batches: rows made one after another
+/// while originals are added), [32] the rows of those, [33] the batches whose
+/// descriptors exceed the executor's on-chip table, [34] the batches whose
+/// window exceeds the executor's on-chip stage, and [35] a constant: the
+/// window elements that stage holds on this device (0: no stage; [34] then
+/// stays 0); count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

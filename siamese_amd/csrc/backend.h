@@ -72,6 +72,11 @@ void be_launch_ingest(const BeIngest& ingest);
 /// skips the rows: a chained device elimination that failed, ops.h GeDesc).
 void be_launch_exec(const void* stream, const ExecItem* items, uint32_t count, uint64_t* acct,
                     const uint32_t* results, uint32_t maxWindow);
+/// Window elements the executor's LDS stage holds at most (fixed by be_init
+/// from the device's LDS and the kernel's static share of it): an OP_ROWS
+/// batch that reads more elements (GfOp.valid - stageLo) reads those past the
+/// stage from memory.  0: the backend has no stage, no batch exceeds it.
+uint32_t be_exec_stage_cap();
 /// Wide rows' LDPC picks (ops.h LdpcItem), one workgroup per item; adds the
 /// reference's source bytes of the picks (min(len, n) each) to acct[0].
 /// gates (or null: every item runs): one word per item, 0 or 1 + a word of

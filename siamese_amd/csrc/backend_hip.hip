@@ -366,7 +366,7 @@ constexpr unsigned kRingWords = 256;         // prefetched words per op (threads
 #define SGPU_STAGE_PRE 2
 #endif
 constexpr unsigned kStagePre = SGPU_STAGE_PRE;   // stage entries per thread fetched a tile ahead (<= 4: VGPRs)
-constexpr unsigned kRowsTableLds = 1024;     // sum + window descriptors of an OP_ROWS batch in LDS
+// (kRowsTableLds, the sum + window descriptors of an OP_ROWS batch in LDS: ops.h)
 constexpr unsigned kPlanCap = 8192;          // planned row terms (LDS slot indices) per batch
 constexpr unsigned kPlanRows = 256;          // rows of a batch that get a plan
 constexpr uint32_t kNoPlan = 0xffffffffu;    // row not planned: general path, counts its bytes
@@ -5121,6 +5121,8 @@ bool be_init(int device, const char** err)
 }
 
 const char* be_name() { return "hip-gfx950"; }
+
+uint32_t be_exec_stage_cap() { return g_stageCap; }
 
 
 #ifdef SGPU_PHASE_CLOCKS

@@ -1143,7 +1143,8 @@ SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count)
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
-    const uint64_t v[30] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const Engine* e = Engine::global();
+    const uint64_t v[36] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
@@ -1151,8 +1152,10 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
                             s.delivers,   s.frames,      s.scans,      Engine::global()->walks(),
                             s.relays,     Engine::global()->packs(),
                             Engine::global()->duplexes(), Engine::global()->ack_frames(),
-                            Engine::global()->concats()};
-    for (unsigned k = 0; k < count && k < 30; ++k)
+                            Engine::global()->concats(),
+                            e->rows_shape(0), e->rows_shape(1), e->rows_shape(2), e->rows_shape(3),
+                            e->rows_shape(4), be_exec_stage_cap()};
+    for (unsigned k = 0; k < count && k < 36; ++k)
         out[k] = v[k];
 }
 

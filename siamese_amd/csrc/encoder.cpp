@@ -526,6 +526,10 @@ void EncoderCore::start_window(unsigned column)
 {
     // :163-181 -- element % 8 == column % 8 is an invariant of the window
     const unsigned element = column % kLanes;
+    // window indices start over below: close the open row batch first, or a
+    // row of the new window made in the same submission as one of the old
+    // would find its elements in the old window's snapshot (remove_elements)
+    prog_.rows_seal();
     // every element of the old window was acknowledged: slabs start afresh
     for (auto& sw : subwindows_)
         release_subwindow(sw.get());

@@ -2136,6 +2136,8 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     std::vector<SolveItem> sitems;
     size_t nOps = 0, nTerms = 0, nWords = 0, nItems = 0, nWide = 0;
     uint64_t wideBytes = 0, tBytes = 0;
+    uint64_t rowsShape[kRowsShapeStats] = {0, 0, 0, 0, 0};
+    const uint32_t stageCap = be_exec_stage_cap();
     for (int g = 0; g < 2; ++g) {
         size_t maxSegs = 0;
         for (ProgramBody* p : bt.bodies[g])
@@ -2151,8 +2153,17 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
                 if (s.ops.empty())
                     continue;
                 for (const GfOp& op : s.ops)
-                    if (op.kind == OP_ROWS)
+                    if (op.kind == OP_ROWS) {
                         ex.maxRows = ex.maxRows == kNoRows ? op.valid : std::max(ex.maxRows, op.valid);
+                        // which of the executor's modes the batch's shape selects
+                        // (sgpu_engine_stats_ex [30..34]; rows_close wrote the header)
+                        const uint32_t stageLo = std::min((uint32_t)op.dst, op.valid), rv = (uint32_t)(op.dst >> 32);
+                        ++rowsShape[0];
+                        rowsShape[1] += rv ? 1 : 0;
+                        rowsShape[2] += rv;
+                        rowsShape[3] += op.termCount > kRowsTableLds + stageLo ? 1 : 0;
+                        rowsShape[4] += stageCap && op.valid - stageLo > stageCap ? 1 : 0;
+                    }
                 const size_t words = kOpWords * s.ops.size() + s.terms.size() + s.rowsWords;
                 segs.push_back(SegRef{&s, (uint32_t)nWords, (uint32_t)words, 0});
                 segs.back().resultBase = bt.resultBase[g][pi];
@@ -2755,6 +2766,9 @@ void Engine::assemble_batch(Batch& bt, WorkerPool& wp)
     st.launches = phases.size() + (nIngest ? 1 : 0) + (gdescs.empty() ? 0 : 1) + (nDeliver ? 1 : 0) +
                   (nFrame ? 1 : 0) + (nRelay ? 1 : 0) + (nPackJob ? 1 : 0) + (nPack ? 1 : 0) +
                   (nConcatJob ? 1 : 0) + (nConcat ? 1 : 0);
+    for (unsigned k = 0; k < kRowsShapeStats; ++k)
+        if (rowsShape[k])
+            rowsShape_[k].fetch_add(rowsShape[k], std::memory_order_relaxed);
     st.delivers = nDeliver;
     st.frames = nFrame;
     st.relays = nRelay;

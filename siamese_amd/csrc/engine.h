@@ -970,8 +970,16 @@ private:
     std::atomic<uint64_t> ackFrames_{0};
     // stream items queued (sgpu_decoder_deliver_stream), counted as packs_ ([29]); here for the same reason
     std::atomic<uint64_t> concats_{0};
+    // the OP_ROWS batches laid out, by the executor mode their shape selects: [0] all of them, [1] the
+    // versioned ones (ops.h RowItem.cutoff), [2] the rows of those, [3] those whose block exceeds the
+    // executor's LDS table (ops.h kRowsTableLds), [4] those whose window exceeds its stage
+    // (be_exec_stage_cap); counted when their submission is laid out (sgpu_engine_stats_ex [30..34]); here
+    // for the same reason
+    static constexpr unsigned kRowsShapeStats = 5;
+    std::atomic<uint64_t> rowsShape_[kRowsShapeStats] = {};
 
 public:
+    uint64_t rows_shape(unsigned k) const { return rowsShape_[k].load(std::memory_order_relaxed); }
     uint64_t walks() const { return walks_.load(std::memory_order_relaxed); }
     uint64_t packs() const { return packs_.load(std::memory_order_relaxed); }
     uint64_t concats() const { return concats_.load(std::memory_order_relaxed); }

@@ -155,6 +155,11 @@ static_assert(sizeof(RowItem) == 48, "RowItem layout");
 constexpr unsigned kRowSums = 24;                       // kLanes * kSums
 constexpr unsigned kUpdateWords = sizeof(SumUpdate) / 16;
 constexpr unsigned kRowWords = sizeof(RowItem) / 16;
+/// Words of an OP_ROWS block the executor keeps in its LDS table: the 24 sum
+/// entries, then the block's words from window element stageLo on.  A batch
+/// whose block, less the stageLo entries it skips, is longer reads the rest
+/// from the stream (Engine counts those batches, sgpu_engine_stats_ex [33]).
+constexpr unsigned kRowsTableLds = 1024;
 
 /// Wide rows (ldpcN >= kLdpcSplitMin): the O(window) LDPC part of a row is
 /// too much for the one workgroup per tile that runs the codec's op list, so

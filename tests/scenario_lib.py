@@ -161,11 +161,15 @@ def run_batch(library, cfg, steps=1, warmup=0, verify=True, device=-1, threads=0
 ENGINE_KEYS = ("flushes launches ops terms solves ingests upload_bytes ref_op_bytes "
                "out_bytes solve_bytes assemble_ns wait_ns complete_ns reclaim_ns "
                "exec_launches ldpc_bytes exec_unique_bytes ge_jobs ge_chained ge_retried "
-               "arena_growth").split()
+               "arena_growth "
+               # sgpu_engine_stats_ex [21..35] (a BatchReport carries the 21 before them)
+               "delivers frames scans walks relays packs duplexes ack_frames concats "
+               "rows_batches rows_versioned rows_versioned_rows rows_unfit rows_unstaged "
+               "stage_cap").split()
 
 
 def engine_dict(report):
-    return {k: int(report.engine[i]) for i, k in enumerate(ENGINE_KEYS)}
+    return {k: int(v) for k, v in zip(ENGINE_KEYS, report.engine)}
 
 
 class BatchSession:

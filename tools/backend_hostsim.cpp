@@ -330,6 +330,10 @@ bool be_init(int, const char** err)
 
 const char* be_name() { return "hostsim (test only)"; }
 
+// (every window element is read from memory here: no stage, so no batch is
+// counted as exceeding one)
+uint32_t be_exec_stage_cap() { return 0; }
+
 void* be_dev_alloc(size_t bytes)
 {
     void* p = nullptr;

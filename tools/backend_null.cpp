@@ -49,6 +49,8 @@ bool be_init(int, const char** err)
 
 const char* be_name() { return "null (profiling only)"; }
 
+uint32_t be_exec_stage_cap() { return 0; }
+
 void* be_dev_alloc(size_t bytes)
 {
     void* p = nullptr;
