@@ -645,6 +645,75 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_packed(const SgpuDecoder* decoders
                                                      size_t stride, unsigned count,
                                                      SiameseResult* results /* count*maxFrames, optional */,
                                                      unsigned* acceptedOut);
+/*
+    The packed scan in dense form.  sgpu_frames_scan_packed's output is sized by
+    the fullest row the receiver might see: count * maxFrames records cross to
+    the host whatever the rows hold.  The dense scan runs the same walk under
+    the same per-frame rules and puts the accepted records of all rows back to
+    back, so the caller sizes the output by the frames it expects in all:
+
+        bytes  = sgpu_frames_dense_bytes(count, maxRecords);      // pinned, sgpu_host_alloc
+        ticket = sgpu_frames_scan_dense(rows, stride, lens, count, maxFrames, maxRecords, out);
+        sgpu_gather_wait(ticket);
+        sgpu_frames_recv_dense(decoders, n, out, maxFrames, maxRecords, rows, stride, count,
+                               results, &rowsDone, &accepted);
+        // rowsDone < count: scan again from row rowsDone
+
+    out holds, little-endian and in this order:
+      - info, four uint32 {T, W, c, 0};
+      - count row words, word k exactly what sgpu_frames_scan_packed writes for
+        row k with the same maxFrames;
+      - count + 1 start words: start[0] = 0, start[k+1] = start[k] +
+        SGPU_PACKED_COUNT(word k), T = start[count];
+      - zeros up to the next 16-byte boundary, sgpu_frames_dense_records(count);
+      - maxRecords SgpuPackedHead records.
+    Rows are all or nothing: c is the largest value with start[c] <= maxRecords
+    and W = start[c].  Records [start[k], start[k+1]) for k < c are byte for
+    byte the first records the packed scan writes for row k (Offset stays
+    relative to that row); records [W, maxRecords) are zero.  Every byte is
+    written by every scan.  maxRecords >= maxFrames, so a scan of at least one
+    row completes at least one row.
+*/
+/// Bytes of a dense scan's output (0 for maxRecords == 0 or above count * 256).
+SIAMESE_EXPORT size_t sgpu_frames_dense_bytes(unsigned count, unsigned maxRecords);
+/// Byte offset of record 0 in a dense scan's output.
+SIAMESE_EXPORT size_t sgpu_frames_dense_records(unsigned count);
+/// sgpu_frames_scan_packed into the dense layout above (pinnedOut: pinned,
+/// 16-byte aligned, sgpu_frames_dense_bytes), with three kernel launches and
+/// one copy: the gather ticket, sgpu_gather_wait, what may be read and what
+/// later submissions wait for are the packed scan's.  Returns -1, with nothing
+/// queued, where sgpu_frames_scan_packed does, for maxFrames outside 1..256,
+/// maxRecords < maxFrames, maxRecords > count * maxFrames (no scan can need
+/// that many) or an output of 4 GiB or more.  count == 0 returns a valid ticket
+/// that is already complete, and nothing is written.
+SIAMESE_EXPORT long long sgpu_frames_scan_dense(const void* deviceRows, size_t stride, const unsigned* deviceLens,
+                                                unsigned count, unsigned maxFrames, unsigned maxRecords,
+                                                void* pinnedOut);
+/// Host only: sgpu_frames_recv_packed for a dense scan's output (`heads`, 4-byte
+/// aligned).  The records of rows [0, c) are routed in order, record i of row k
+/// having its data at deviceRows + k*stride + Offset + HeaderBytes.  results[i]
+/// (optional, maxRecords entries) = the result for record i;
+/// Siamese_NeedMoreData for slots from W on.  *rowsOut = c, the rows routed:
+/// when it is below count, scan again from that row.  *acceptedOut = the frames
+/// handed to a decoder.  A row whose word has SGPU_PACKED_MALFORMED contributes
+/// Siamese_InvalidInput to the return value after its good frames have been
+/// delivered.  The output is caller data and never trusted: info is copied, and
+/// c <= count, W <= maxRecords, start[0] == 0, non-decreasing starts,
+/// start[k+1] - start[k] == min(SGPU_PACKED_COUNT(word k), maxFrames) for
+/// k < c and start[c] == W are checked before a row's records are touched, and
+/// each record is copied and checked against stride as sgpu_frames_recv_packed
+/// checks one.  At the first start that fails, routing stops, *rowsOut = the
+/// rows routed before it and the call returns Siamese_InvalidInput; a record
+/// that fails, or a word whose count exceeds maxFrames, counts as malformed.
+/// Arguments are refused as in sgpu_frames_recv_packed, for a null rowsOut and
+/// for the sizes sgpu_frames_scan_dense refuses.  For well-formed rows the
+/// decoders end in the state sgpu_frames_recv_packed leaves them in on the same
+/// rows.
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                    const void* heads, unsigned maxFrames, unsigned maxRecords,
+                                                    const void* deviceRows, size_t stride, unsigned count,
+                                                    SiameseResult* results /* maxRecords, optional */,
+                                                    unsigned* rowsOut, unsigned* acceptedOut);
 /// Queue a stream's frames packed into MTU-sized rows: the present originals
 /// firstPacketNum .. firstPacketNum+originalCount-1 of `encoder`, ascending, as
 /// SGPU_FRAME_ORIGINAL, then `recovery` (this encoder's current output) as
@@ -943,7 +1012,9 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// likewise), [9] k_relay (sgpu_decoder_deliver_frames), [10] k_plan and [11]
 /// k_pack (sgpu_decoder_pack_frames), [12] k_ackwalk (sgpu_frames_scan_duplex,
 /// counted as k_walk is), [13] k_offsets and [14] k_concat
-/// (sgpu_decoder_deliver_stream); count entries at most.
+/// (sgpu_decoder_deliver_stream), [15] k_rowsum and [16] k_compact
+/// (sgpu_frames_scan_dense, counted as k_walk is; the dense scan's walk is
+/// counted under [8]); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -979,7 +1050,8 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// descriptors exceed the executor's on-chip table, [34] the batches whose
 /// window exceeds the executor's on-chip stage, and [35] a constant: the
 /// window elements that stage holds on this device (0: no stage; [34] then
-/// stays 0); count entries at most.
+/// stays 0), then [36] the rows scanned by sgpu_frames_scan_dense, counted as
+/// [24]; count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

@@ -71,6 +71,22 @@ def bind_packed_abi(L):
     return L
 
 
+def bind_dense_abi(L):
+    """Prototypes of the dense packed scan (sgpu_frames_scan_dense and
+    sgpu_frames_recv_dense) and of bind_packed_abi's calls."""
+    vp, u, sz = ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t
+    bind_packed_abi(L)
+    L.sgpu_frames_dense_bytes.restype = sz
+    L.sgpu_frames_dense_bytes.argtypes = [u, u]
+    L.sgpu_frames_dense_records.restype = sz
+    L.sgpu_frames_dense_records.argtypes = [u]
+    L.sgpu_frames_scan_dense.restype = ctypes.c_longlong
+    L.sgpu_frames_scan_dense.argtypes = [vp, sz, vp, u, u, u, vp]
+    L.sgpu_frames_recv_dense.restype = ctypes.c_int
+    L.sgpu_frames_recv_dense.argtypes = [vp, u, vp, u, u, vp, sz, u, vp, vp, vp]
+    return L
+
+
 def bind_relay_pack_abi(L):
     """Prototype of sgpu_decoder_pack_frames: a decoder's packets as wire
     frames packed several to a row, laid out on the device."""

@@ -230,6 +230,16 @@ bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint3
 bool be_ackwalk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
                      uint32_t ackSlots, uint32_t ackBytes, void* devStage, void* hostOut, void** packed,
                      void** landed);
+/// The packed scan in dense form (ops.h dense_bytes): three launches on the
+/// gather stream -- k_walk's walk with the row's records into the scratch area
+/// at dense_scratch_offset(count, maxRecords) and the row words into the output,
+/// k_rowsum for the starts and the info words, k_compact for the records -- all
+/// into devStage (dense_stage_bytes(count, maxFrames, maxRecords), device
+/// memory, 16-byte aligned), then one copy of the first dense_bytes(count,
+/// maxRecords) bytes to hostOut (pinned), without waiting.  rows, stride, lens
+/// and the marks are be_scan_rows'.
+bool be_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                   uint32_t maxRecords, void* devStage, void* hostOut, void** packed, void** landed);
 /// Block until the device has passed `mark`, then recycle it; false on a
 /// device fault.
 bool be_mark_sync(void* mark);
@@ -237,8 +247,9 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-/// (kBeScan, kBeWalk and kBeAckWalk are bracketed on the gather stream: be_sync waits for a
-/// bracket of those classes still in flight before it folds it in)
+/// (kBeScan, kBeWalk, kBeAckWalk, kBeRowsum and kBeCompact are bracketed on the gather stream:
+/// be_sync waits for a bracket of those classes still in flight before it folds it in; the dense
+/// scan's walk is counted as kBeWalk)
 enum BeKernel
 {
     kBeIngest,
@@ -256,6 +267,8 @@ enum BeKernel
     kBeAckWalk,
     kBeOffsets,
     kBeConcat,
+    kBeRowsum,
+    kBeCompact,
     kBeKernelKinds
 };
 void be_timing_enable(bool on);

@@ -29,6 +29,9 @@
 //                  into caller-owned rows (header, packet, zero tail; opt-in)
 //   k_scan         frame rows in device memory into 32-byte host records
 //   k_walk         rows that hold several frames into one record per frame
+//   k_walkd, k_rowsum, k_compact  k_walk's records of all rows back to back: the
+//                  walk into device scratch, a prefix sum over the rows' counts,
+//                  then a placed copy
 //   k_ackwalk      k_walk with acknowledgement frames, their messages into slots
 //                  (header fields, a recovery packet's head and tail; opt-in)
 //
@@ -4567,16 +4570,12 @@ __device__ __forceinline__ uint64_t low_bytes64(int64_t n)
     return n <= 0 ? 0ull : (n >= 8 ? ~0ull : (((uint64_t)1 << (8 * n)) - 1));
 }
 
-__global__ __launch_bounds__(kWalkThreads) void k_walk(uint64_t rows, uint64_t stride,
-                                                       const uint32_t* __restrict__ lens, uint32_t count,
-                                                       uint32_t maxFrames, uint64_t out)
+// One row's walk, shared by k_walk and k_walkd: the accepted frames' records
+// go to rec, n of them, and the row word n | flags is returned.  Records past
+// the n-th are not written here.
+__device__ __forceinline__ uint32_t walk_row(uint64_t row, uint64_t stride, uint64_t end, uint32_t maxFrames,
+                                             uint64_t rec)
 {
-    const uint64_t k = (uint64_t)blockIdx.x * kWalkThreads + threadIdx.x;
-    if (k >= count)
-        return;
-    const uint64_t row = rows + k * stride;
-    const uint64_t rec = out + k * maxFrames * 32;
-    uint64_t end = lens ? lens[k] : stride;
     uint32_t n = 0, flags = 0;
     if (end > stride) {
         flags = kPackedMalformed;
@@ -4664,11 +4663,206 @@ __global__ __launch_bounds__(kWalkThreads) void k_walk(uint64_t rows, uint64_t s
         ++n;
         at += total;
     }
-    for (uint32_t j = n; j < maxFrames; ++j) {   // every record is written by every scan
+    return n | flags;
+}
+
+__global__ __launch_bounds__(kWalkThreads) void k_walk(uint64_t rows, uint64_t stride,
+                                                       const uint32_t* __restrict__ lens, uint32_t count,
+                                                       uint32_t maxFrames, uint64_t out)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kWalkThreads + threadIdx.x;
+    if (k >= count)
+        return;
+    const uint64_t rec = out + k * maxFrames * 32;
+    const uint32_t word = walk_row(rows + k * stride, stride, lens ? lens[k] : stride, maxFrames, rec);
+    for (uint32_t j = word & kPackedCountMask; j < maxFrames; ++j) {   // every record is written by every scan
         st16(rec + (uint64_t)j * 32, make_uint4(0, 0, 0, 0));
         st16(rec + (uint64_t)j * 32 + 16, make_uint4(0, 0, 0, 0));
     }
-    *reinterpret_cast<GMEM uint32_t*>(out + (uint64_t)count * maxFrames * 32 + k * 4) = n | flags;
+    *reinterpret_cast<GMEM uint32_t*>(out + (uint64_t)count * maxFrames * 32 + k * 4) = word;
+}
+
+// ---------------------------------------------------------------------------
+// Dense packed scan (k_walkd, k_rowsum, k_compact; ops.h dense_bytes,
+// frames.h dense_compact is the statement)
+//
+// k_walk's records without the slots no frame filled: the walk writes each
+// row's records into a scratch area that stays on the device, a prefix sum over
+// the rows' counts places them, and a copy packs them back to back, so the bytes
+// that cross to the host follow the frames there are and not count * maxFrames.
+
+// k_walkd: k_walk's lane per row and walk_row, the records into the row's
+// maxFrames scratch slots (those past the n-th stay unwritten: k_compact reads
+// none of them) and the row word into the output's word table.
+__global__ __launch_bounds__(kWalkThreads) void k_walkd(uint64_t rows, uint64_t stride,
+                                                        const uint32_t* __restrict__ lens, uint32_t count,
+                                                        uint32_t maxFrames, uint64_t scratch, uint64_t words)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kWalkThreads + threadIdx.x;
+    if (k >= count)
+        return;
+    *reinterpret_cast<GMEM uint32_t*>(words + k * 4) =
+        walk_row(rows + k * stride, stride, lens ? lens[k] : stride, maxFrames, scratch + k * maxFrames * 32);
+}
+
+// inclusive sum of v over the lanes of a wave up to this one (six __shfl_up
+// steps: k_offsets' scan on 32-bit values, which the rows' counts fit)
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, uint32_t lane)
+{
+#pragma unroll
+    for (unsigned s = 1; s < 64; s <<= 1) {
+        const uint32_t u = __shfl_up(v, s);
+        if (lane >= s)
+            v += u;
+    }
+    return v;
+}
+
+// k_rowsum: start[] = the exclusive prefix sum of the rows' counts, and from it
+// c, W, T, the info words and the zero padding before the records.  The carry
+// scheme is a single workgroup striding over the rows: kRowsumThreads lanes,
+// lane t of a pass owning the kRowsumRows consecutive rows from base + t *
+// kRowsumRows, so a pass covers kRowsumPass rows and the running sum of the
+// passes before is a register that every lane holds.  Within a pass a lane sums
+// its rows, the wave scans the lane sums (wave_incl_sum), lane 63 of each wave
+// leaves the wave's sum in LDS and, after one barrier, every lane adds the sums
+// of the waves before its own.  The table of wave sums is double-buffered by the
+// pass's parity, so one barrier per pass is enough: a wave that writes pass
+// p + 2's sums has passed pass p + 1's barrier, which no wave reaches before it
+// has read pass p's.  This was chosen over a two-level block-sum pass because it
+// is one launch without a second kernel or a grid-wide wait, its order of
+// additions is fixed by the row index alone, and it is short beside the walk: 40
+// passes for 327,680 rows, with the next pass's words loaded (two 16-byte loads
+// per lane) before this pass's scan so that their latency is hidden.  A count
+// above maxFrames, which the walk never writes, is clamped, so a row's span in
+// the scratch area can never be left.  Rows are complete while start[k + 1] <=
+// maxRecords; the starts only grow, so the number of such rows is c and the
+// largest such start is W: both are reduced over the workgroup through LDS,
+// integers in a fixed order.  No atomics.
+__global__ __launch_bounds__(kRowsumThreads) void k_rowsum(uint64_t out, uint32_t count, uint32_t maxFrames,
+                                                           uint32_t maxRecords)
+{
+    constexpr uint32_t kWaves = kRowsumThreads / 64;
+    __shared__ uint32_t wsum[2][kWaves];
+    __shared__ uint32_t redC[kWaves], redW[kWaves];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t words = out + 16, starts = words + (uint64_t)count * 4;
+    auto load = [&](uint32_t base, uint32_t* n) {
+        const uint64_t r0 = (uint64_t)base + tid * kRowsumRows;
+        if (r0 + kRowsumRows <= count) {   // (16-byte aligned: base and kRowsumRows are multiples of 4)
+            const uint4 a = ld16(words + r0 * 4), b = ld16(words + r0 * 4 + 16);
+            n[0] = a.x, n[1] = a.y, n[2] = a.z, n[3] = a.w;
+            n[4] = b.x, n[5] = b.y, n[6] = b.z, n[7] = b.w;
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < kRowsumRows; ++j)
+                n[j] = r0 + j < count ? *reinterpret_cast<const GMEM uint32_t*>(words + (r0 + j) * 4) : 0u;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kRowsumRows; ++j) {
+            n[j] &= kPackedCountMask;
+            n[j] = n[j] < maxFrames ? n[j] : maxFrames;
+        }
+    };
+    static_assert(kRowsumRows == 8, "k_rowsum loads a lane's rows as two 16-byte words");
+    uint32_t carry = 0, done = 0, W = 0;
+    uint32_t nx[kRowsumRows];
+    load(0, nx);
+    for (uint32_t base = 0, p = 0; base < count; base += kRowsumPass, p ^= 1) {
+        uint32_t n[kRowsumRows];
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kRowsumRows; ++j) {
+            n[j] = nx[j];
+            s += n[j];
+        }
+        if (count - base > kRowsumPass)
+            load(base + kRowsumPass, nx);
+        const uint32_t incl = wave_incl_sum(s, lane);
+        if (lane == 63)
+            wsum[p][wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kWaves; ++w) {
+            const uint32_t v = wsum[p][w];
+            total += v;
+            before += w < wave ? v : 0u;
+        }
+        uint32_t at = carry + before + incl - s;
+        const uint64_t r0 = (uint64_t)base + tid * kRowsumRows;
+#pragma unroll
+        for (uint32_t j = 0; j < kRowsumRows; ++j) {
+            if (r0 + j < count) {
+                *reinterpret_cast<GMEM uint32_t*>(starts + (r0 + j) * 4) = at;
+                at += n[j];
+                if (at <= maxRecords) {
+                    ++done;
+                    W = at;
+                }
+            }
+        }
+        carry += total;
+    }
+    // c = the sum of done, W = the largest W (0 where no row is complete)
+#pragma unroll
+    for (unsigned s = 32; s >= 1; s >>= 1) {
+        done += __shfl_xor(done, s);
+        const uint32_t o = __shfl_xor(W, s);
+        W = W > o ? W : o;
+    }
+    if (lane == 0) {
+        redC[wave] = done;
+        redW[wave] = W;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t c = 0, w = 0;
+        for (uint32_t i = 0; i < kWaves; ++i) {
+            c += redC[i];
+            w = w > redW[i] ? w : redW[i];
+        }
+        *reinterpret_cast<GMEM uint32_t*>(starts + (uint64_t)count * 4) = carry;
+        for (uint64_t a = starts + (uint64_t)(count + 1) * 4; a < out + dense_records_offset(count); a += 4)
+            *reinterpret_cast<GMEM uint32_t*>(a) = 0;
+        st16(out, make_uint4(carry, w, c, 0));
+    }
+}
+
+// k_compact: one record slot of the output per pair of lanes, each lane one
+// 16-byte half, over all maxRecords slots: a wave stores 1 KiB of consecutive
+// bytes.  Slot i < W belongs to the row k with start[k] <= i < start[k + 1]
+// (rows without frames share a start with the next row and own no slot): a
+// binary search over start[0, c], whose two ends hold 0 and W, so k < c always;
+// the table is count + 1 words that every lane reads and stays in cache.  The
+// slot is record i - start[k] of row k's scratch span (below maxFrames, by
+// k_rowsum's clamp); a slot from W on is zero.  No LDS, no atomics.
+__global__ __launch_bounds__(kCompactThreads) void k_compact(uint64_t out, uint64_t scratch, uint32_t count,
+                                                             uint32_t maxFrames, uint32_t maxRecords)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * kCompactThreads + threadIdx.x;
+    const uint64_t i = g >> 1;
+    if (i >= maxRecords)
+        return;
+    const uint64_t half = (g & 1) * 16;
+    const uint4 info = ld16(out);   // {T, W, c, 0}
+    const uint32_t c = info.z < count ? info.z : count;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (i < info.y && c != 0) {
+        const uint64_t starts = out + 16 + (uint64_t)count * 4;
+        uint32_t lo = 0, hi = c;   // start[lo] <= i < start[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (*reinterpret_cast<const GMEM uint32_t*>(starts + (uint64_t)mid * 4) <= i)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const uint64_t j = i - *reinterpret_cast<const GMEM uint32_t*>(starts + (uint64_t)lo * 4);
+        if (j < maxFrames)
+            v = ld16(scratch + ((uint64_t)lo * maxFrames + j) * 32 + half);
+    }
+    st16(out + dense_records_offset(count) + i * 32 + half, v);
 }
 
 // ---------------------------------------------------------------------------
@@ -4943,7 +5137,8 @@ void harvest_timing(bool all)
         if (!all && hipEventQuery(ev.b) != hipSuccess)
             break;
         // (a synchronised codec stream says nothing about the gather stream)
-        if (all && (ev.kind == kBeScan || ev.kind == kBeWalk || ev.kind == kBeAckWalk))
+        if (all && (ev.kind == kBeScan || ev.kind == kBeWalk || ev.kind == kBeAckWalk || ev.kind == kBeRowsum ||
+                    ev.kind == kBeCompact))
             (void)hipEventSynchronize(ev.b);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.a, ev.b);
@@ -5875,6 +6070,50 @@ bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint3
         return false;
     *packed = p;
     if (hipMemcpyAsync(hostOut, devStage, (size_t)packed_bytes(count, maxFrames), hipMemcpyDeviceToHost,
+                       g_gatherStream) != hipSuccess ||
+        hipEventRecord(l, g_gatherStream) != hipSuccess) {
+        be_mark_release(l);
+        return false;
+    }
+    *landed = l;
+    return true;
+}
+
+bool be_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                   uint32_t maxRecords, void* devStage, void* hostOut, void** packed, void** landed)
+{
+    bind_device();
+    *packed = *landed = nullptr;
+    hipEvent_t p = take_mark(), l = take_mark();
+    if (!p || !l) {
+        be_mark_release(p);
+        be_mark_release(l);
+        return false;
+    }
+    const uint64_t out = (uint64_t)(uintptr_t)devStage;
+    const uint64_t scratch = out + dense_scratch_offset(count, maxRecords);
+    {
+        Timed t(kBeWalk, g_gatherStream);
+        hipLaunchKernelGGL(k_walkd, dim3((count + kWalkThreads - 1) / kWalkThreads), dim3(kWalkThreads), 0,
+                           g_gatherStream, (uint64_t)(uintptr_t)rows, stride, lens, count, maxFrames, scratch,
+                           out + 16);
+    }
+    // (the rows have been read: what follows works on the staging area alone)
+    if (hipEventRecord(p, g_gatherStream) != hipSuccess)
+        return false;
+    *packed = p;
+    {
+        Timed t(kBeRowsum, g_gatherStream);
+        hipLaunchKernelGGL(k_rowsum, dim3(1), dim3(kRowsumThreads), 0, g_gatherStream, out, count, maxFrames,
+                           maxRecords);
+    }
+    {
+        Timed t(kBeCompact, g_gatherStream);
+        const uint64_t lanes = 2 * (uint64_t)maxRecords;
+        hipLaunchKernelGGL(k_compact, dim3((uint32_t)((lanes + kCompactThreads - 1) / kCompactThreads)),
+                           dim3(kCompactThreads), 0, g_gatherStream, out, scratch, count, maxFrames, maxRecords);
+    }
+    if (hipMemcpyAsync(hostOut, devStage, (size_t)dense_bytes(count, maxRecords), hipMemcpyDeviceToHost,
                        g_gatherStream) != hipSuccess ||
         hipEventRecord(l, g_gatherStream) != hipSuccess) {
         be_mark_release(l);

@@ -857,6 +857,118 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_packed(const SgpuDecoder* decoders
     return status;
 }
 
+namespace {
+// the sizes sgpu_frames_dense_bytes, sgpu_frames_scan_dense and sgpu_frames_recv_dense share
+inline bool dense_ok(unsigned count, unsigned maxFrames, unsigned maxRecords)
+{
+    return maxFrames >= 1 && maxFrames <= kPackedMaxFrames && maxRecords >= maxFrames &&
+           (uint64_t)maxRecords <= (uint64_t)count * maxFrames;
+}
+} // namespace
+
+SIAMESE_EXPORT size_t sgpu_frames_dense_bytes(unsigned count, unsigned maxRecords)
+{
+    // (what no maxFrames allows: fewer than one record, more than 256 per row)
+    return maxRecords >= 1 && (uint64_t)maxRecords <= (uint64_t)count * kPackedMaxFrames
+               ? (size_t)dense_bytes(count, maxRecords)
+               : 0;
+}
+
+SIAMESE_EXPORT size_t sgpu_frames_dense_records(unsigned count)
+{
+    return (size_t)dense_records_offset(count);
+}
+
+SIAMESE_EXPORT long long sgpu_frames_scan_dense(const void* deviceRows, size_t stride, const unsigned* deviceLens,
+                                                unsigned count, unsigned maxFrames, unsigned maxRecords,
+                                                void* pinnedOut)
+{
+    if (!g_batchReady || !rows_ok(deviceRows, stride, count) || ((uintptr_t)deviceLens & 3) ||
+        ((uintptr_t)pinnedOut & 15) || (!pinnedOut && count > 0) || maxFrames < 1 || maxFrames > kPackedMaxFrames ||
+        packed_bytes(count, maxFrames) > ((uint64_t)1 << 32))
+        return -1;
+    // (count == 0 admits no maxRecords >= maxFrames: its ticket is complete and nothing is written)
+    if (count > 0 && (!dense_ok(count, maxFrames, maxRecords) || dense_bytes(count, maxRecords) >= ((uint64_t)1 << 32)))
+        return -1;
+    return (long long)Engine::global()->dense_rows_async(deviceRows, stride, deviceLens, count, maxFrames,
+                                                         count ? maxRecords : 0, pinnedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                    const void* heads, unsigned maxFrames, unsigned maxRecords,
+                                                    const void* deviceRows, size_t stride, unsigned count,
+                                                    SiameseResult* results, unsigned* rowsOut,
+                                                    unsigned* acceptedOut)
+{
+    if (rowsOut)
+        *rowsOut = 0;
+    if (!acceptedOut)
+        return Siamese_InvalidInput;
+    *acceptedOut = 0;
+    if (!rowsOut || !rows_ok(deviceRows, stride, count) || ((!decoders || !heads) && count > 0) ||
+        ((uintptr_t)heads & 3) || maxFrames < 1 || maxFrames > kPackedMaxFrames ||
+        (count > 0 && !dense_ok(count, maxFrames, maxRecords)))
+        return Siamese_InvalidInput;
+    if (count == 0)
+        return Siamese_Success;
+    for (unsigned i = 0; results && i < maxRecords; ++i)
+        results[i] = Siamese_NeedMoreData;
+    // (the output is the caller's memory: every word and record is copied, checked and only then used)
+    const uint64_t dev = (uint64_t)(uintptr_t)deviceRows;
+    const uint8_t* base = static_cast<const uint8_t*>(heads);
+    const uint8_t* words = base + 16;
+    const uint8_t* starts = words + (size_t)count * 4;
+    const uint8_t* recs = base + (size_t)dense_records_offset(count);
+    uint32_t info[4];
+    std::memcpy(info, base, sizeof(info));
+    const uint32_t W = info[1], c = info[2];
+    if (c > count || W > maxRecords)
+        return Siamese_InvalidInput;
+    unsigned accepted = 0;
+    SiameseResult status = Siamese_Success;
+    uint32_t at = 0;   // start[k], checked
+    std::memcpy(&at, starts, 4);
+    bool forged = at != 0;
+    unsigned k = 0;
+    for (; !forged && k < c; ++k) {
+        uint32_t word, next;
+        std::memcpy(&word, words + (size_t)k * 4, 4);
+        std::memcpy(&next, starts + (size_t)(k + 1) * 4, 4);
+        unsigned n = word & kPackedCountMask;
+        bool malformed = (word & kPackedMalformed) != 0;
+        const unsigned span = n < maxFrames ? n : maxFrames;
+        // the row's records are [at, next): non-decreasing, as many as its word says, and before W
+        if (next < at || next - at != span || next > W) {
+            forged = true;
+            break;
+        }
+        if (n > maxFrames) {   // (no scan writes such a word: none of the row's records is used)
+            n = 0;
+            malformed = true;
+        }
+        for (unsigned j = 0; j < n; ++j) {
+            PackedHead h;
+            std::memcpy(&h, recs + ((size_t)at + j) * sizeof(h), sizeof(h));
+            SiameseResult r = Siamese_InvalidInput;
+            if (packed_head_valid(h, stride))
+                r = route_head(decoders, decoderCount, h, dev + (uint64_t)k * stride + h.offset + h.headerBytes,
+                               &accepted);
+            if (results)
+                results[at + j] = r;
+            if (r != Siamese_Success && r != Siamese_NeedMoreData && status == Siamese_Success)
+                status = r;
+        }
+        if (malformed && status == Siamese_Success)   // (the frame the walk stopped at has no slot here)
+            status = Siamese_InvalidInput;
+        at = next;
+    }
+    if (!forged && at != W)
+        forged = true;
+    *rowsOut = k;   // c, unless the table stopped the routing before it
+    *acceptedOut = accepted;
+    return forged ? Siamese_InvalidInput : status;
+}
+
 SIAMESE_EXPORT SiameseResult sgpu_encoder_pack_frames(SgpuEncoder encoder, unsigned flow, unsigned firstPacketNum,
                                                       unsigned originalCount, const SgpuRecoveryPacket* recovery,
                                                       unsigned recoveryCount, void* deviceDst, size_t stride,
@@ -1144,7 +1256,7 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
     const Engine* e = Engine::global();
-    const uint64_t v[36] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[37] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
@@ -1154,8 +1266,9 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
                             Engine::global()->duplexes(), Engine::global()->ack_frames(),
                             Engine::global()->concats(),
                             e->rows_shape(0), e->rows_shape(1), e->rows_shape(2), e->rows_shape(3),
-                            e->rows_shape(4), be_exec_stage_cap()};
-    for (unsigned k = 0; k < count && k < 36; ++k)
+                            e->rows_shape(4), be_exec_stage_cap(),
+                            e->denses()};
+    for (unsigned k = 0; k < count && k < 37; ++k)
         out[k] = v[k];
 }
 

@@ -3164,9 +3164,11 @@ int64_t Engine::gather_async_framed(unsigned count, const void* const* srcs, con
 }
 
 // scan_rows_async (maxFrames == 0: k_scan) and walk_rows_async (k_walk)
-// and duplex_rows_async (ackSlots != 0: k_ackwalk)
+// and duplex_rows_async (ackSlots != 0: k_ackwalk) and dense_rows_async
+// (maxRecords != 0: k_walkd, k_rowsum and k_compact)
 int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
-                           unsigned maxFrames, void* pinnedOut, unsigned ackSlots, unsigned ackBytes)
+                           unsigned maxFrames, void* pinnedOut, unsigned ackSlots, unsigned ackBytes,
+                           unsigned maxRecords)
 {
     if (failed())
         return -1;
@@ -3177,8 +3179,10 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     GatherSlot& g = gslots_[ticket % kGatherSlots];
     if (!gather_land(g))   // (the slot's previous gather, kGatherSlots back)
         return -1;
-    // the records take the slot's packing area; a scan uploads no descriptors
-    const size_t total = ackSlots    ? (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes)
+    // the records take the slot's packing area (the dense scan's scratch records behind its output); a scan
+    // uploads no descriptors
+    const size_t total = maxRecords  ? (size_t)dense_stage_bytes(count, maxFrames, maxRecords)
+                         : ackSlots  ? (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes)
                          : maxFrames ? (size_t)packed_bytes(count, maxFrames)
                                      : (size_t)count * sizeof(RowHead);
     if (total > g.stageCap) {
@@ -3193,7 +3197,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     if (!g.stage)
         return -1;
     void* packed = nullptr;
-    if (!(ackSlots    ? be_ackwalk_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, g.stage, pinnedOut,
+    if (!(maxRecords  ? be_dense_rows(rows, stride, lens, count, maxFrames, maxRecords, g.stage, pinnedOut, &packed,
+                                      &g.landed)
+          : ackSlots  ? be_ackwalk_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, g.stage, pinnedOut,
                                         &packed, &g.landed)
           : maxFrames ? be_walk_rows(rows, stride, lens, count, maxFrames, g.stage, pinnedOut, &packed, &g.landed)
                       : be_scan_rows(rows, stride, lens, count, g.stage, pinnedOut, &packed, &g.landed))) {
@@ -3201,7 +3207,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
         return -1;
     }
     g.ticket = ticket;
-    if (ackSlots)
+    if (maxRecords)
+        denses_.fetch_add(count, std::memory_order_relaxed);
+    else if (ackSlots)
         duplexes_.fetch_add(count, std::memory_order_relaxed);
     else if (maxFrames)
         walks_.fetch_add(count, std::memory_order_relaxed);

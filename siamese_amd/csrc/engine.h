@@ -784,6 +784,16 @@ public:
     {
         return rows_async(rows, stride, lens, count, maxFrames, pinnedOut, ackSlots, ackBytes);
     }
+    /// The packed scan with the accepted records of all rows back to back
+    /// behind a table of per-row starts: dense_bytes(count, maxRecords) in all,
+    /// into pinnedOut (k_walkd, k_rowsum and k_compact, sgpu_frames_scan_dense).
+    /// maxFrames <= maxRecords <= count * maxFrames.  The slot's staging area
+    /// also holds the walk's per-row scratch records, which stay on the device.
+    int64_t dense_rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
+                             unsigned maxFrames, unsigned maxRecords, void* pinnedOut)
+    {
+        return rows_async(rows, stride, lens, count, maxFrames, pinnedOut, 0, 0, maxRecords);
+    }
     /// Wait until gather `ticket` and every earlier one have landed.
     bool gather_wait(int64_t ticket);
     /// Host -> device copy on the staging stream, issued now; every later
@@ -957,7 +967,7 @@ private:
     int64_t gNext_ = 0;
     bool gather_land(GatherSlot& g);
     int64_t rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count, unsigned maxFrames,
-                       void* pinnedOut, unsigned ackSlots = 0, unsigned ackBytes = 0);
+                       void* pinnedOut, unsigned ackSlots = 0, unsigned ackBytes = 0, unsigned maxRecords = 0);
     // rows scanned by the packed scan, counted when the scan is queued (sgpu_engine_stats_ex [24]); kept
     // here, behind every other member, and not in EngineStats, whose size every submission's counters share
     std::atomic<uint64_t> walks_{0};
@@ -970,6 +980,8 @@ private:
     std::atomic<uint64_t> ackFrames_{0};
     // stream items queued (sgpu_decoder_deliver_stream), counted as packs_ ([29]); here for the same reason
     std::atomic<uint64_t> concats_{0};
+    // rows scanned by the dense scan, counted as walks_ ([36]); here for the same reason
+    std::atomic<uint64_t> denses_{0};
     // the OP_ROWS batches laid out, by the executor mode their shape selects: [0] all of them, [1] the
     // versioned ones (ops.h RowItem.cutoff), [2] the rows of those, [3] those whose block exceeds the
     // executor's LDS table (ops.h kRowsTableLds), [4] those whose window exceeds its stage
@@ -983,6 +995,7 @@ public:
     uint64_t walks() const { return walks_.load(std::memory_order_relaxed); }
     uint64_t packs() const { return packs_.load(std::memory_order_relaxed); }
     uint64_t concats() const { return concats_.load(std::memory_order_relaxed); }
+    uint64_t denses() const { return denses_.load(std::memory_order_relaxed); }
     uint64_t duplexes() const { return duplexes_.load(std::memory_order_relaxed); }
     uint64_t ack_frames() const { return ackFrames_.load(std::memory_order_relaxed); }
     void count_ack_frames(uint64_t n) { ackFrames_.fetch_add(n, std::memory_order_relaxed); }

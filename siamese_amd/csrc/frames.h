@@ -258,6 +258,43 @@ inline uint32_t row_walk(const uint8_t* row, uint64_t stride, const uint32_t* le
     return n;
 }
 
+/// What k_rowsum and k_compact compute from the walk's output (ops.h
+/// dense_bytes states the layout, sgpu_frames_scan_dense / sgpu_frames_recv_dense
+/// use it): words = the count row words, rowRecs = maxFrames records per row as
+/// row_walk writes them, out = dense_bytes(count, maxRecords) bytes, every one of
+/// which is written.  The starts are the exclusive prefix sum of the words'
+/// counts (a count above maxFrames, which no walk writes, counts as maxFrames);
+/// rows are all or nothing: c is the largest value with start[c] <= maxRecords,
+/// the records of rows [0, c) lie back to back from record 0 and the records
+/// from W = start[c] on are zero.
+inline void dense_compact(const uint32_t* words, const PackedHead* rowRecs, uint32_t count, uint32_t maxFrames,
+                          uint32_t maxRecords, uint8_t* out)
+{
+    const size_t recAt = (size_t)dense_records_offset(count);
+    std::memset(out, 0, (size_t)dense_bytes(count, maxRecords));
+    uint8_t* wordsOut = out + 16;
+    uint8_t* starts = wordsOut + (size_t)count * 4;
+    uint32_t sum = 0, c = 0, W = 0;
+    for (uint32_t k = 0; k < count; ++k) {
+        const uint32_t w = words[k];
+        uint32_t n = w & kPackedCountMask;
+        if (n > maxFrames)
+            n = maxFrames;
+        std::memcpy(wordsOut + (size_t)k * 4, &w, 4);
+        std::memcpy(starts + (size_t)k * 4, &sum, 4);
+        if ((uint64_t)sum + n <= maxRecords) {   // (the sums only grow: false once, false ever after)
+            std::memcpy(out + recAt + (size_t)sum * sizeof(PackedHead), rowRecs + (size_t)k * maxFrames,
+                        (size_t)n * sizeof(PackedHead));
+            c = k + 1;
+            W = sum + n;
+        }
+        sum += n;
+    }
+    std::memcpy(starts + (size_t)count * 4, &sum, 4);
+    const uint32_t info[4] = {sum, W, c, 0};
+    std::memcpy(out, info, 16);
+}
+
 /// Rows of a bidirectional flow (ops.h kRowTruncated, sgpu_frames_scan_duplex /
 /// sgpu_frames_recv_duplex).  The one definition of an ack record that a duplex
 /// scan with these ackSlots and ackBytes can have produced for a row of

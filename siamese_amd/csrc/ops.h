@@ -673,6 +673,47 @@ constexpr uint64_t duplex_bytes(uint64_t count, uint64_t maxFrames, uint64_t ack
     return duplex_slots_offset(count, maxFrames) + count * ackSlots * ackBytes;
 }
 
+/// The packed scan's records without the empty slots (k_walkd, k_rowsum and
+/// k_compact, sgpu_frames_scan_dense): the accepted records of all rows back to
+/// back in row order, behind a table of per-row start indices.  The output is
+///   info {T, W, c, 0} | count row words | count + 1 start words | zeros to the
+///   next 16-byte boundary | maxRecords PackedHead records
+/// where row word k is k_walk's, n_k its count, start[0] = 0, start[k + 1] =
+/// start[k] + n_k, T = start[count], c the largest value with start[c] <=
+/// maxRecords and W = start[c].  Records [start[k], start[k + 1]) for k < c are
+/// row k's first n_k records as k_walk writes them (offset relative to the row);
+/// records [W, maxRecords) are zero (frames.h dense_compact states all of it).
+/// maxFrames <= maxRecords <= count * maxFrames, so c >= 1 for count >= 1.
+///
+/// On the device the walk writes each row's records into a scratch area of
+/// count * maxFrames records behind the output (dense_scratch_offset), which
+/// never crosses to the host.  k_rowsum is one workgroup of kRowsumThreads
+/// lanes that strides over the rows, kRowsumRows consecutive rows per lane and
+/// so kRowsumPass rows per pass; k_compact takes one record slot per pair of
+/// lanes, kCompactThreads lanes per workgroup.
+constexpr uint32_t kRowsumThreads = 1024;
+constexpr uint32_t kRowsumRows = 8;
+constexpr uint32_t kRowsumPass = kRowsumThreads * kRowsumRows;
+constexpr uint32_t kCompactThreads = 256;
+/// Where a dense scan's records start, its output's bytes, and where the
+/// device's scratch records start in the staging area.
+constexpr uint64_t dense_records_offset(uint64_t count)
+{
+    return (16 + count * 4 + (count + 1) * 4 + 15) & ~(uint64_t)15;
+}
+constexpr uint64_t dense_bytes(uint64_t count, uint64_t maxRecords)
+{
+    return dense_records_offset(count) + maxRecords * sizeof(PackedHead);
+}
+constexpr uint64_t dense_scratch_offset(uint64_t count, uint64_t maxRecords)
+{
+    return dense_bytes(count, maxRecords);   // (a multiple of 16)
+}
+constexpr uint64_t dense_stage_bytes(uint64_t count, uint64_t maxFrames, uint64_t maxRecords)
+{
+    return dense_scratch_offset(count, maxRecords) + count * maxFrames * sizeof(PackedHead);
+}
+
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)
 /// Solves with more rows than this stage 256-byte tiles (16 lanes x 16 bytes

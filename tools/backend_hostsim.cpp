@@ -752,6 +752,23 @@ bool be_walk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint3
     return true;
 }
 
+// k_walkd, k_rowsum and k_compact (ops.h dense_bytes): frames.h row_walk per
+// row into the scratch area, then frames.h dense_compact.
+bool be_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
+                   uint32_t maxRecords, void* devStage, void* hostOut, void** packed, void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    uint8_t* out = static_cast<uint8_t*>(devStage);
+    PackedHead* scratch = reinterpret_cast<PackedHead*>(out + (size_t)dense_scratch_offset(count, maxRecords));
+    std::vector<uint32_t> words(count);
+    for (uint32_t k = 0; k < count; ++k)
+        words[k] = row_walk(static_cast<const uint8_t*>(rows) + (uint64_t)k * stride, stride,
+                            lens ? lens + k : nullptr, maxFrames, scratch + (size_t)k * maxFrames);
+    dense_compact(words.data(), scratch, count, maxFrames, maxRecords, out);
+    std::memcpy(hostOut, devStage, (size_t)dense_bytes(count, maxRecords));
+    return true;
+}
+
 // k_ackwalk (ops.h kRowTruncated): frames.h ack_walk per row, the row words
 // after the records and the slots from the next 16-byte boundary on.
 bool be_ackwalk_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,

@@ -147,6 +147,16 @@ bool be_walk_rows(const void*, uint64_t, const uint32_t*, uint32_t count, uint32
     return true;
 }
 
+bool be_dense_rows(const void*, uint64_t, const uint32_t*, uint32_t count, uint32_t, uint32_t maxRecords,
+                   void* devStage, void* hostOut, void** packed, void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    std::memset(devStage, 0, (size_t)dense_bytes(count, maxRecords));
+    std::memcpy(static_cast<uint8_t*>(devStage) + 8, &count, 4);   // info {0, 0, c = count, 0}
+    std::memcpy(hostOut, devStage, (size_t)dense_bytes(count, maxRecords));
+    return true;
+}
+
 bool be_ackwalk_rows(const void*, uint64_t, const uint32_t*, uint32_t count, uint32_t maxFrames, uint32_t ackSlots,
                      uint32_t ackBytes, void* devStage, void* hostOut, void** packed, void** landed)
 {

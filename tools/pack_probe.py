@@ -20,7 +20,23 @@ look at them, timed in the same process, interleaved, after a warm-up:
 
 The medians are reported, with every repetition.
 
-    python tools/pack_probe.py [--flows 1024] [--rows 320] [--frames 8] [--reps 9] [--out FILE]
+--dense adds two legs that compare sgpu_frames_scan_packed with
+sgpu_frames_scan_dense (k_walk's walk, k_rowsum, k_compact) on the same rows,
+both with maxFrames = --frames, interleaved in the same process:
+
+  all-full    the rows as above, every row full: maxRecords = rows x frames, so
+              the dense form brings more bytes than the packed one (the starts
+              and the info words) and shows what its two extra launches and the
+              scratch round trip cost;
+  mixed-fill  the same rows with length words that end row k behind its
+              f_k-th frame, f_k drawn uniformly from 1..frames with a fixed
+              seed (mean (frames + 1) / 2, the mean drawn is reported):
+              maxRecords = the known total rounded up to a multiple of 1024.
+
+For each: the bytes to the host, the median and range of scan plus wait, and
+the device time of each kernel (sgpu_timing_kernels [8], [15], [16]).
+
+    python tools/pack_probe.py [--flows 1024] [--rows 320] [--frames 8] [--reps 9] [--dense] [--out FILE]
 
 Needs an MI355X: without one the library refuses to initialise and the probe
 fails (no CPU fallback; --library with the CPU test double rehearses the call
@@ -49,6 +65,66 @@ def hip_runtime():
     sys.exit("pack_probe: no HIP runtime in the process")
 
 
+def dense_legs(L, a, dev, lens, rows, nf, stride, ends, rehearsal):
+    """The all-full and the mixed-fill leg: packed against dense on the same rows."""
+    med = statistics.median
+    legs = {}
+    rng = random.Random(11)
+    fills = [rng.randrange(1, nf + 1) for _ in range(rows)]
+    for leg in ("all_full", "mixed_fill"):
+        if leg == "mixed_fill":
+            # (every frame's header has the same width here, so the first row's frame ends hold for all rows)
+            lraw = b"".join(ends[f - 1].to_bytes(4, "little") for f in fills)
+            assert L.sgpu_h2d(lens, lraw, len(lraw)) == 0
+            total = sum(fills)
+            maxRecords = min(rows * nf, (total + 1023) & ~1023)
+        else:
+            total = maxRecords = rows * nf
+        pBytes = L.sgpu_frames_packed_bytes(rows, nf)
+        dBytes = L.sgpu_frames_dense_bytes(rows, maxRecords)
+        pOut, dOut = L.sgpu_host_alloc(pBytes), L.sgpu_host_alloc(dBytes)
+        assert pOut and dOut
+
+        def timed(call):
+            L.sgpu_timing(1, 1, None, None)
+            t0 = time.perf_counter()
+            t = call()
+            assert t > 0 and L.sgpu_gather_wait(t) == 0
+            wall = (time.perf_counter() - t0) * 1e3
+            ms = (C.c_double * 17)()
+            L.sgpu_timing_kernels(ms, 17)
+            return wall, list(ms)
+
+        pw, pk, dw, dk = [], [], [], []
+        for r in range(a.warmup + a.reps):
+            w1, m1 = timed(lambda: L.sgpu_frames_scan_packed(dev, stride, lens, rows, nf, pOut))
+            w2, m2 = timed(lambda: L.sgpu_frames_scan_dense(dev, stride, lens, rows, nf, maxRecords, dOut))
+            if r >= a.warmup:
+                pw.append(w1)
+                pk.append(m1[8])
+                dw.append(w2)
+                dk.append((m2[8], m2[15], m2[16]))
+        info = (C.c_uint * 4).from_address(dOut)
+        assert list(info) == [total, total, rows, 0], "dense info %r, expected T = W = %d" % (list(info), total)
+        words = (C.c_uint * rows).from_address(pOut + rows * nf * 32)   # (behind the 32-byte records)
+        assert sum(words) == total
+        res = {"frames": total, "mean_frames_per_row": round(total / rows, 4), "max_records": maxRecords,
+               "packed_bytes": pBytes, "dense_bytes": dBytes}
+        if not rehearsal:
+            res.update({"packed_wait_ms_median": round(med(pw), 4), "packed_wait_ms_range": [round(min(pw), 4), round(max(pw), 4)],
+                        "dense_wait_ms_median": round(med(dw), 4), "dense_wait_ms_range": [round(min(dw), 4), round(max(dw), 4)],
+                        "packed_k_walk_ms_median": round(med(pk), 4),
+                        "dense_k_walk_ms_median": round(med([k[0] for k in dk]), 4),
+                        "k_rowsum_ms_median": round(med([k[1] for k in dk]), 4),
+                        "k_compact_ms_median": round(med([k[2] for k in dk]), 4),
+                        "packed_wait_ms": [round(v, 4) for v in pw], "dense_wait_ms": [round(v, 4) for v in dw],
+                        "dense_over_packed": round(med(dw) / med(pw), 3)})
+        legs[leg] = res
+        L.sgpu_host_free(pOut)
+        L.sgpu_host_free(dOut)
+    return legs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--library", default=os.path.join(ROOT, "siamese_amd", "libsiamese_amd.so"))
@@ -59,16 +135,18 @@ def main():
     ap.add_argument("--stride", type=int, default=1424)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--dense", action="store_true", help="add the all-full and mixed-fill legs of the dense scan")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     rehearsal = "hostsim" in os.path.basename(a.library)
 
-    from siamese_amd.binding import ROW_OK, PackedHead, RowHead, bind_packed_abi
-    L = bind_packed_abi(C.CDLL(a.library))
+    from siamese_amd.binding import ROW_OK, PackedHead, RowHead, bind_dense_abi
+    L = bind_dense_abi(C.CDLL(a.library))
     L.sgpu_device_alloc.restype = C.c_void_p
     L.sgpu_device_alloc.argtypes = [C.c_size_t]
     L.sgpu_host_alloc.restype = C.c_void_p
     L.sgpu_host_alloc.argtypes = [C.c_size_t]
+    L.sgpu_host_free.argtypes = [C.c_void_p]
     L.sgpu_h2d.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.sgpu_frame_write_header.restype = C.c_uint
     L.sgpu_frame_write_header.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
@@ -94,6 +172,7 @@ def main():
     dev = L.sgpu_device_alloc(total)
     lens = L.sgpu_device_alloc(4 * rows)
     assert dev and lens
+    ends = []   # where each frame of a row ends (the same in every row but for the header's width)
     for i in range(n):
         block, lw = [], []
         for r in range(per):
@@ -102,6 +181,8 @@ def main():
                 row += bytes(-len(row) % 16)
                 row += (header(0, i, r * (nf - 1) + j, size) + data[j][:size]) if j < nf - 1 else \
                     (header(1, i, 0, rsize) + data[j])
+                if i == 0 and r == 0:
+                    ends.append(len(row))
             assert len(row) <= stride
             lw.append(len(row).to_bytes(4, "little"))
             block.append(bytes(row) + bytes(stride - len(row)))
@@ -155,6 +236,7 @@ def main():
             sc.append(s)
             kn.append(k)
             cp.append(c)
+    dense = dense_legs(L, a, dev, lens, rows, nf, stride, ends, rehearsal) if a.dense else None
     L.sgpu_timing(0, 1, None, None)
 
     # spot check: first and last flow, first and last row, every frame
@@ -185,6 +267,8 @@ def main():
                     "k_walk_frames_per_us": round(rows * nf / (med(wn) * 1e3), 1) if med(wn) else None})
     else:
         out["rehearsal"] = "CPU test double: call sequence only, no time"
+    if dense:
+        out["dense"] = dense
     line = json.dumps(out)
     print(line)
     if a.out:
