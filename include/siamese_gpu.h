@@ -1051,7 +1051,13 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// window exceeds the executor's on-chip stage, and [35] a constant: the
 /// window elements that stage holds on this device (0: no stage; [34] then
 /// stays 0), then [36] the rows scanned by sgpu_frames_scan_dense, counted as
-/// [24]; count entries at most.
+/// [24], then [37] the recovery-matrix eliminations that met a zero pivot and
+/// went on with row pivoting, on the host or in a device job (its pivot order
+/// is not the identity, or it stopped short of the last column), counted when
+/// the elimination's outcome is known -- a singular device job counts here
+/// once, and the host's repeat of its elimination, which pivots again, once
+/// more -- and [38] the device jobs, chained or not, that came back singular;
+/// count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

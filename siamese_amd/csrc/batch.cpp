@@ -1256,7 +1256,7 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
     const Engine* e = Engine::global();
-    const uint64_t v[37] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[39] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
@@ -1267,8 +1267,8 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
                             Engine::global()->concats(),
                             e->rows_shape(0), e->rows_shape(1), e->rows_shape(2), e->rows_shape(3),
                             e->rows_shape(4), be_exec_stage_cap(),
-                            e->denses()};
-    for (unsigned k = 0; k < count && k < 37; ++k)
+                            e->denses(),  s.gePivoted,   s.geSingular};
+    for (unsigned k = 0; k < count && k < 39; ++k)
         out[k] = v[k];
 }
 

@@ -1731,6 +1731,7 @@ SiameseResult DecoderCore::decode_region()
         g_decodeClocks.sample(d);
     }
     region_reset();
+    geHost_ = false;   // (the region is solved: the next one's first attempt may go to the device)
     return res;
 }
 
@@ -1747,6 +1748,7 @@ SiameseResult DecoderCore::finish_region(bool solved)
     }
     const SiameseResult res = solve_and_substitute();
     region_reset();
+    geHost_ = false;   // (as decode_region)
     return res;
 }
 
@@ -2006,7 +2008,10 @@ SiameseResult DecoderCore::finish_chained(SiameseOriginalPacket** packetsOut, un
         // as decode() does.
         drop_solve();
         chain_sums_restore();
-        eng_->shard().stats.geRetried++;
+        EngineStats& st = eng_->shard().stats;
+        st.geRetried++;
+        st.geSingular++;
+        st.gePivoted++;   // (it stopped in the pivoted phase)
         geHost_ = true;
         matrix_reset();
         return decode_loop(packetsOut, countOut);
@@ -2019,6 +2024,7 @@ SiameseResult DecoderCore::finish_chained(SiameseOriginalPacket** packetsOut, un
     eng_->account(deferredBytes_);
     eng_->account((uint64_t)o[4] * chainBytes_, 0, true);
     const uint8_t* piv = reinterpret_cast<const uint8_t*>(o + ge_out_pivots(geRows_));
+    count_device_pivoting(piv, geRows_);
     scratchRec_.resize(columns);
     scratchLen_.resize(columns);
     for (unsigned i = 0; i < columns; ++i) {
@@ -2084,6 +2090,9 @@ SiameseResult DecoderCore::finish_device_ge(SiameseOriginalPacket** packetsOut, 
         // the elimination stopped short of a pivot: the host repeats it (the
         // resumable state the reference keeps for the next attempt), and the
         // search goes on as decode() does
+        EngineStats& st = eng_->shard().stats;
+        st.geSingular++;
+        st.gePivoted++;   // (it stopped in the pivoted phase)
         geHost_ = true;
         matrix_reset();
         return decode_loop(packetsOut, countOut);
@@ -2092,6 +2101,7 @@ SiameseResult DecoderCore::finish_device_ge(SiameseOriginalPacket** packetsOut, 
     const uint8_t* used = reinterpret_cast<const uint8_t*>(o + ge_out_used(rows));
     const uint16_t* cnt = reinterpret_cast<const uint16_t*>(o + ge_out_counts(rows));
     const uint8_t* mat = reinterpret_cast<const uint8_t*>(o + ge_out_matrix(rows));
+    count_device_pivoting(piv, rows);
     pivots_.resize(rows);
     for (unsigned i = 0; i < rows; ++i) {
         pivots_[i] = piv[i];
@@ -2107,6 +2117,18 @@ SiameseResult DecoderCore::finish_device_ge(SiameseOriginalPacket** packetsOut, 
         *countOut = (unsigned)recovered_.size();
     }
     return res;
+}
+
+// An eliminated device job took a pivoted step exactly when its pivot order
+// is not the identity: the step that leaves the no-pivot loop found a zero at
+// [p][p] and swaps a later position into p.
+void DecoderCore::count_device_pivoting(const uint8_t* piv, unsigned rows)
+{
+    for (unsigned i = 0; i < rows; ++i)
+        if (piv[i] != i) {
+            eng_->shard().stats.gePivoted++;
+            return;
+        }
 }
 
 void DecoderCore::chain_sums_commit()
@@ -2442,6 +2464,7 @@ bool DecoderCore::pivoted_ge(unsigned pivot)
 {
     const unsigned columns = matCols_;
     const unsigned rows = matRows_;
+    eng_->shard().stats.gePivoted++;
     unsigned j = pivot + 1; // the caller already found column `pivot` zero here
     bool resume = true;
     for (; pivot < columns; ++pivot) {

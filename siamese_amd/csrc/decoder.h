@@ -415,6 +415,7 @@ private:
     }
     void chain_sums_commit();    // the elimination ran: release what it replaced
     void chain_sums_restore();   // it did not: back to chainSums_
+    void count_device_pivoting(const uint8_t* piv, unsigned rows);
     bool generate_matrix();
     void populate_columns(unsigned oldColumns, unsigned newColumns);
     void populate_rows(unsigned oldRows, unsigned newRows);
@@ -533,8 +534,10 @@ private:
     std::vector<unsigned> geEnd_;   // gaussian_elimination: each pivot row's column count
     unsigned geResume_ = 0;
     // a device elimination came out singular: this decoder's later attempts
-    // eliminate on the host, in the round that runs their symbol work (a
-    // lone device job is a 48 us latency-bound launch on the step's tail)
+    // at the same region eliminate on the host, in the round that runs their
+    // symbol work (a lone device job is a 48 us latency-bound launch on the
+    // step's tail), also after a block's next packet reset the region;
+    // cleared once a region is solved
     bool geHost_ = false;
     uint64_t geBytes_ = 0;   // coefficient bytes the elimination multiplied (accounting)
     // the current pivot row's bytes after the pivot, split for gf_muladd_prepared

@@ -51,6 +51,8 @@ void EngineStats::add(const EngineStats& o)
     geChained += o.geChained;
     geRetried += o.geRetried;
     geChainedWide += o.geChainedWide;
+    gePivoted += o.gePivoted;
+    geSingular += o.geSingular;
     delivers += o.delivers;
     frames += o.frames;
     scans += o.scans;

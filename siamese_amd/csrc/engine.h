@@ -657,6 +657,11 @@ struct EngineStats
     // their decode's submission, chained ones that found a singular matrix
     uint64_t geJobs = 0, geChained = 0, geRetried = 0;
     uint64_t geChainedWide = 0;   // chained jobs whose decode carried gated k_ldpc items (wide rows)
+    // eliminations that left the no-pivot loop, on the host (pivoted_ge entered) or on the device (a
+    // pivot order other than the identity, or a stop short of the last column), counted when the
+    // outcome is known (a singular device job and the host's repeat of it count one each); device
+    // jobs, chained or not, that came back singular
+    uint64_t gePivoted = 0, geSingular = 0;
     uint64_t delivers = 0;        // delivery items queued (sgpu_decoder_deliver_range)
     uint64_t frames = 0;          // frame items queued (sgpu_frames_deliver_recovery, sgpu_encoder_deliver_range)
     uint64_t scans = 0;           // rows scanned (sgpu_frames_scan_rows), counted when the scan is queued

@@ -361,10 +361,12 @@ def stage_cap(path):
 
 
 class Run:
-    """A case's schedule queued on one encoder and one decoder, unflushed."""
+    """A case's schedule queued on one encoder and one decoder, unflushed.
+    With `schedule`, only that much of it: play() queues more later
+    (ge_cases.py: a decode between two parts of a stream)."""
 
-    def __init__(self, L, case, data):
-        self.L, self.case = L, case
+    def __init__(self, L, case, data, schedule=None):
+        self.L, self.case, self.data = L, case, data
         count = len(case.lengths)
         # (originals at odd device addresses, as deliver_cases.Stream lays them out)
         self.pitch = ((max(case.lengths) + 34) & ~15) + 2
@@ -379,20 +381,25 @@ class Run:
         # recovery packet k bare in row k: the longest symbol and its footer fit
         self.recRows = D.Rows(L, case.recovery, (max(case.lengths) + 3 + 8 + 15) & ~15)
         self.recs = (D.Rec * case.recovery)()
-        added = made = 0
-        for op, n in case.schedule:
+        self.added = self.made = 0
+        self.play(case.schedule if schedule is None else schedule)
+
+    def play(self, schedule):
+        L, case, data = self.L, self.case, self.data
+        for op, n in schedule:
             if op == "add":
-                for i in range(added, added + n):
+                for i in range(self.added, self.added + n):
                     num = C.c_uint(0)
                     assert L.sgpu_encoder_add(self.enc, self.at(i), len(data[i]), C.byref(num)) == D.SUCCESS
                     assert num.value == i
                     if i not in case.lost:
                         assert L.sgpu_decoder_add_original(self.dec, i, self.at(i), len(data[i])) == D.SUCCESS
-                added += n
+                self.added += n
             elif op == "remove_before":
                 assert L.sgpu_encoder_remove_before(self.enc, n) == D.SUCCESS
             else:
                 for _ in range(n):
+                    made = self.made
                     r = self.recs[made]
                     assert L.sgpu_encode(self.enc, C.byref(r)) == D.SUCCESS
                     queued = C.c_uint(0)
@@ -400,7 +407,7 @@ class Run:
                         1, C.byref(r), None, self.recRows.dst + made * self.recRows.stride, self.recRows.stride,
                         self.recRows.lens + 4 * made, C.byref(queued)) == D.SUCCESS and queued.value == 1
                     assert L.sgpu_decoder_add_recovery(self.dec, C.byref(r)) == D.SUCCESS
-                    made += 1
+                    self.made += 1
 
     def at(self, i):
         return self.src + 3 + i * self.pitch

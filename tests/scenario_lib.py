@@ -165,7 +165,9 @@ ENGINE_KEYS = ("flushes launches ops terms solves ingests upload_bytes ref_op_by
                # sgpu_engine_stats_ex [21..35] (a BatchReport carries the 21 before them)
                "delivers frames scans walks relays packs duplexes ack_frames concats "
                "rows_batches rows_versioned rows_versioned_rows rows_unfit rows_unstaged "
-               "stage_cap").split()
+               "stage_cap "
+               # [36..38]
+               "denses ge_pivoted ge_singular").split()
 
 
 def engine_dict(report):

@@ -13,6 +13,7 @@
 #include "../siamese_amd/csrc/frames.h"
 
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -908,7 +909,7 @@ void be_launch_ge(const BeGe& ge, GePlace place, const BeCopy& head)
             for (unsigned k = p + 1; k < rows; ++k)
                 elim(p, k, p, cnt[p], val);
         }
-        unsigned stop = cols;
+        unsigned stop = cols, grown = 0;   // (grown: column counts a pivoted step raised, for the trace)
         if (p < cols) {
             unsigned j = p + 1;
             for (unsigned pivot = p; pivot < cols; ++pivot) {
@@ -929,12 +930,26 @@ void be_launch_ge(const BeGe& ge, GePlace place, const BeCopy& head)
                 const uint8_t val = M[(size_t)rj * cols + pivot];
                 for (unsigned k = pivot + 1; k < rows; ++k) {
                     const unsigned rk = piv[k];
-                    if (elim(rj, rk, pivot, end, val) && cnt[rk] < end)
+                    if (elim(rj, rk, pivot, end, val) && cnt[rk] < end) {
                         cnt[rk] = (uint16_t)end;
+                        ++grown;
+                    }
                 }
             }
         }
         const bool ok = stop == cols;
+        // HOSTSIM_GE_TRACE=1 (tools/find_ge_cases.py): a line per job with its
+        // shape, the first zero pivot (cols: none), where it stopped and how
+        // many column counts its pivoted steps raised, then its parity,
+        // Cauchy and Siamese rows
+        if (std::getenv("HOSTSIM_GE_TRACE")) {
+            unsigned kinds[3] = {0, 0, 0};
+            for (unsigned r = 0; r < rows; ++r)
+                kinds[R[r].kind == GE_PARITY ? 0 : R[r].kind == GE_CAUCHY ? 1 : 2]++;
+            std::fprintf(stderr, "hostsim ge: rows %u cols %u chained %u pickLen %u first_zero %u stop %u grown %u "
+                         "kinds %u %u %u\n", rows, cols, (d.flags & kGeChained) ? 1u : 0u, d.pickLen, p, stop, grown,
+                         kinds[0], kinds[1], kinds[2]);
+        }
         uint32_t nz = 0;   // non-zero multipliers below the diagonal, pivot order
         if (ok)
             for (unsigned j = 0; j < cols; ++j)
