@@ -998,6 +998,102 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex(const SgpuDecoder* decoders
                                                      SiameseResult* results /* count*maxFrames, optional */,
                                                      unsigned* nextExpectedOut /* count*maxFrames, optional */,
                                                      unsigned* acceptedOut);
+/*
+    The duplex scan in dense form.  sgpu_frames_scan_duplex ships count *
+    maxFrames records and count * ackSlots slots whatever the rows hold, and
+    acknowledgements are rare.  The dense duplex scan runs the same walk under
+    the same per-frame and per-ack rules and puts the accepted records of all
+    rows back to back, as sgpu_frames_scan_dense does, and the used slots of all
+    rows back to back behind a second table:
+
+        bytes  = sgpu_frames_duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes);   // pinned
+        ticket = sgpu_frames_scan_duplex_dense(rows, stride, lens, count, maxFrames, ackSlots, ackBytes,
+                                               maxRecords, maxAcks, out);
+        sgpu_gather_wait(ticket);
+        sgpu_frames_recv_duplex_dense(decoders, nd, encoders, ne, out, maxFrames, ackSlots, ackBytes,
+                                      maxRecords, maxAcks, rows, stride, count, results, nextExpected,
+                                      &rowsDone, &accepted);
+        // rowsDone < count: scan again from row rowsDone
+
+    out holds, little-endian and in this order:
+      - info, four uint32 {T, W, c, WA};
+      - count row words, word k exactly what sgpu_frames_scan_duplex writes for
+        row k with the same maxFrames, ackSlots and ackBytes;
+      - count + 1 start words: start[0] = 0, start[k+1] = start[k] +
+        SGPU_PACKED_COUNT(word k), T = start[count];
+      - zeros up to sgpu_frames_dense_records(count);
+      - maxRecords SgpuPackedHead records;
+      - count + 1 ack start words, from sgpu_frames_duplex_dense_acks(count,
+        maxRecords): astart[0] = 0, astart[k+1] = astart[k] + min(ack frames of
+        row k, ackSlots);
+      - zeros up to the next 16-byte boundary, sgpu_frames_duplex_dense_slots(
+        count, maxRecords);
+      - maxAcks slots of ackBytes bytes.
+    Up to the end of the records this is sgpu_frames_scan_dense's layout with
+    info word 3 = WA.  Rows are all or nothing over both budgets: c is the
+    largest value with start[c] <= maxRecords and astart[c] <= maxAcks, W =
+    start[c] and WA = astart[c].  Records [start[k], start[k+1]) for k < c are
+    byte for byte the first records the duplex scan writes for row k (Offset
+    relative to that row, PacketNum = the ack's number within its row, Status
+    SGPU_ROW_TRUNCATED under the same per-row ackSlots and ackBytes rule); slot
+    astart[k] + a, for k < c and a < min(acks of row k, ackSlots), is byte for
+    byte row k's slot a of the duplex scan.  An ack with a >= ackSlots has a
+    record and no slot.  Records from W on and slots from WA on are zero.  Every
+    byte is written by every scan.  maxRecords >= maxFrames and maxAcks >=
+    ackSlots, so a scan of at least one row completes at least one row.
+*/
+/// Bytes of a dense duplex scan's output (0 for a maxRecords or maxAcks of 0 or
+/// above count * 256, an ackBytes the duplex scan refuses, or 4 GiB or more).
+SIAMESE_EXPORT size_t sgpu_frames_duplex_dense_bytes(unsigned count, unsigned maxRecords, unsigned maxAcks,
+                                                     unsigned ackBytes);
+/// Byte offset of astart[0] in a dense duplex scan's output (0 where
+/// sgpu_frames_dense_bytes(count, maxRecords) is).
+SIAMESE_EXPORT size_t sgpu_frames_duplex_dense_acks(unsigned count, unsigned maxRecords);
+/// Byte offset of slot 0 in a dense duplex scan's output (0 likewise).
+SIAMESE_EXPORT size_t sgpu_frames_duplex_dense_slots(unsigned count, unsigned maxRecords);
+/// sgpu_frames_scan_duplex into the dense layout above (pinnedOut: pinned,
+/// 16-byte aligned, sgpu_frames_duplex_dense_bytes), with four kernel launches
+/// and one copy: the gather ticket, sgpu_gather_wait, what may be read, what
+/// later submissions wait for and the threading rule are sgpu_frames_scan_dense's.
+/// Returns -1, with nothing queued, where sgpu_frames_scan_duplex does, for
+/// maxRecords < maxFrames, maxRecords > count * maxFrames, maxAcks < ackSlots,
+/// maxAcks > count * ackSlots or an output of 4 GiB or more.  count == 0 returns
+/// a valid ticket that is already complete, and nothing is written.
+SIAMESE_EXPORT long long sgpu_frames_scan_duplex_dense(const void* deviceRows, size_t stride,
+                                                       const unsigned* deviceLens, unsigned count,
+                                                       unsigned maxFrames, unsigned ackSlots, unsigned ackBytes,
+                                                       unsigned maxRecords, unsigned maxAcks, void* pinnedOut);
+/// Host only: sgpu_frames_recv_duplex for a dense duplex scan's output (`heads`,
+/// 4-byte aligned).  The records of rows [0, c) are routed in order and exactly
+/// as sgpu_frames_recv_duplex routes them: data frames to decoders[Flow], an
+/// SGPU_ROW_OK ack from its slot to sgpu_encoder_acknowledge(encoders[Flow]);
+/// a truncated ack and a flow without an instance give Siamese_InvalidInput.
+/// results[i] and nextExpectedOut[i] (optional, maxRecords entries each) belong
+/// to record i; results are Siamese_NeedMoreData for slots from W on.  *rowsOut
+/// = c, the rows routed: when it is below count, scan again from that row.
+/// *acceptedOut = the frames handed to a decoder or an encoder.  The output is
+/// caller data and never trusted: info and every table word are copied; c <=
+/// count, W <= maxRecords, WA <= maxAcks, start[0] == astart[0] == 0,
+/// non-decreasing starts with start[k+1] - start[k] == min(SGPU_PACKED_COUNT(
+/// word k), maxFrames), non-decreasing ack starts with astart[k+1] - astart[k]
+/// == the ack records of row k with PacketNum < ackSlots, start[c] == W and
+/// astart[c] == WA are checked before a row's records are routed, each record is
+/// copied and checked as sgpu_frames_recv_duplex checks one, and no slot outside
+/// the row's own [astart[k], astart[k+1]) is read.  At the first start of either
+/// table that fails, routing stops, *rowsOut = the rows routed before it and the
+/// call returns Siamese_InvalidInput; a record that fails, or a word whose count
+/// exceeds maxFrames, counts as malformed.  Arguments are refused as in
+/// sgpu_frames_recv_duplex, for a null rowsOut and for the sizes the scan
+/// refuses.  For well-formed rows the decoders and encoders end in the state
+/// sgpu_frames_recv_duplex leaves them in on the same rows.
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                           const SgpuEncoder* encoders, unsigned encoderCount,
+                                                           const void* heads, unsigned maxFrames, unsigned ackSlots,
+                                                           unsigned ackBytes, unsigned maxRecords, unsigned maxAcks,
+                                                           const void* deviceRows, size_t stride, unsigned count,
+                                                           SiameseResult* results /* maxRecords, optional */,
+                                                           unsigned* nextExpectedOut /* maxRecords, optional */,
+                                                           unsigned* rowsOut, unsigned* acceptedOut);
 
 /// Device timing of flushed work since the last reset (milliseconds).
 SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* totalMs);
@@ -1014,7 +1110,9 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// counted as k_walk is), [13] k_offsets and [14] k_concat
 /// (sgpu_decoder_deliver_stream), [15] k_rowsum and [16] k_compact
 /// (sgpu_frames_scan_dense, counted as k_walk is; the dense scan's walk is
-/// counted under [8]); count entries at most.
+/// counted under [8]), [17] k_rowsum2 and [18] k_slots
+/// (sgpu_frames_scan_duplex_dense, likewise; its walk is counted under [12] and
+/// its record copy under [16]); count entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -1056,7 +1154,8 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// is not the identity, or it stopped short of the last column), counted when
 /// the elimination's outcome is known -- a singular device job counts here
 /// once, and the host's repeat of its elimination, which pivots again, once
-/// more -- and [38] the device jobs, chained or not, that came back singular;
+/// more -- and [38] the device jobs, chained or not, that came back singular,
+/// then [39] the rows scanned by sgpu_frames_scan_duplex_dense, counted as [36];
 /// count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'

@@ -128,6 +128,26 @@ def bind_duplex_abi(L):
     return L
 
 
+def bind_duplex_dense_abi(L):
+    """Prototypes of the dense duplex scan (sgpu_frames_scan_duplex_dense and
+    sgpu_frames_recv_duplex_dense) and of bind_duplex_abi's and bind_dense_abi's
+    calls."""
+    vp, u, sz = ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t
+    bind_duplex_abi(L)
+    bind_dense_abi(L)
+    L.sgpu_frames_duplex_dense_bytes.restype = sz
+    L.sgpu_frames_duplex_dense_bytes.argtypes = [u, u, u, u]
+    L.sgpu_frames_duplex_dense_acks.restype = sz
+    L.sgpu_frames_duplex_dense_acks.argtypes = [u, u]
+    L.sgpu_frames_duplex_dense_slots.restype = sz
+    L.sgpu_frames_duplex_dense_slots.argtypes = [u, u]
+    L.sgpu_frames_scan_duplex_dense.restype = ctypes.c_longlong
+    L.sgpu_frames_scan_duplex_dense.argtypes = [vp, sz, vp, u, u, u, u, u, u, vp]
+    L.sgpu_frames_recv_duplex_dense.restype = ctypes.c_int
+    L.sgpu_frames_recv_duplex_dense.argtypes = [vp, u, vp, u, vp, u, u, u, u, u, vp, sz, u, vp, vp, vp, vp]
+    return L
+
+
 def bind_stream_abi(L):
     """Prototype of sgpu_decoder_deliver_stream: a decoder's packets as one
     contiguous byte stream at any byte alignment, summed and copied on the

@@ -240,6 +240,18 @@ bool be_ackwalk_rows(const void* rows, uint64_t stride, const uint32_t* lens, ui
 /// and the marks are be_scan_rows'.
 bool be_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count, uint32_t maxFrames,
                    uint32_t maxRecords, void* devStage, void* hostOut, void** packed, void** landed);
+/// The duplex scan in dense form (ops.h duplex_dense_bytes): four launches on
+/// the gather stream -- k_ackwalk's walk with the row's records, slots and ack
+/// count into the scratch areas (duplex_dense_scratch_*) and the row words into
+/// the output, k_rowsum2 for both start tables and the info words, k_compact for
+/// the records, k_slots for the slots -- all into devStage
+/// (duplex_dense_stage_bytes(...), device memory, 16-byte aligned), then one copy
+/// of the first duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes) bytes to
+/// hostOut (pinned), without waiting.  rows, stride, lens and the marks are
+/// be_scan_rows'.
+bool be_duplex_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count,
+                          uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes, uint32_t maxRecords,
+                          uint32_t maxAcks, void* devStage, void* hostOut, void** packed, void** landed);
 /// Block until the device has passed `mark`, then recycle it; false on a
 /// device fault.
 bool be_mark_sync(void* mark);
@@ -247,9 +259,10 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-/// (kBeScan, kBeWalk, kBeAckWalk, kBeRowsum and kBeCompact are bracketed on the gather stream:
-/// be_sync waits for a bracket of those classes still in flight before it folds it in; the dense
-/// scan's walk is counted as kBeWalk)
+/// (kBeScan, kBeWalk, kBeAckWalk, kBeRowsum, kBeCompact, kBeRowsum2 and kBeSlots are bracketed on
+/// the gather stream: be_sync waits for a bracket of those classes still in flight before it folds
+/// it in; the dense scan's walk is counted as kBeWalk, the duplex dense scan's as kBeAckWalk and
+/// its k_compact as kBeCompact)
 enum BeKernel
 {
     kBeIngest,
@@ -269,6 +282,8 @@ enum BeKernel
     kBeConcat,
     kBeRowsum,
     kBeCompact,
+    kBeRowsum2,
+    kBeSlots,
     kBeKernelKinds
 };
 void be_timing_enable(bool on);

@@ -33,6 +33,9 @@
 //                  walk into device scratch, a prefix sum over the rows' counts,
 //                  then a placed copy
 //   k_ackwalk      k_walk with acknowledgement frames, their messages into slots
+//   k_ackwalkd, k_rowsum2, k_slots  k_ackwalk's records (through k_compact) and
+//                  used slots of all rows back to back: the walk into device
+//                  scratch, one prefix sum over both counts, then placed copies
 //                  (header fields, a recovery packet's head and tail; opt-in)
 //
 // GF(256) multiply by a wave-uniform constant uses three v_perm_b32 byte
@@ -4845,7 +4848,7 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(uint64_t out, uint6
     if (i >= maxRecords)
         return;
     const uint64_t half = (g & 1) * 16;
-    const uint4 info = ld16(out);   // {T, W, c, 0}
+    const uint4 info = ld16(out);   // {T, W, c, 0 or the dense duplex scan's WA, which is not read here}
     const uint32_t c = info.z < count ? info.z : count;
     uint4 v = make_uint4(0, 0, 0, 0);
     if (i < info.y && c != 0) {
@@ -4884,18 +4887,15 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(uint64_t out, uint6
 // its slot, or an ack after the row's last slot, is reported as truncated and
 // the walk goes on behind it.  No LDS, no atomics.
 
-__global__ __launch_bounds__(kAckWalkThreads) void k_ackwalk(uint64_t rows, uint64_t stride,
-                                                             const uint32_t* __restrict__ lens, uint32_t count,
-                                                             uint32_t maxFrames, uint32_t ackSlots,
-                                                             uint32_t ackBytes, uint64_t out, uint64_t slots)
+// One row's duplex walk, shared by k_ackwalk and k_ackwalkd: the accepted
+// frames' records go to rec, n of them, each ack's message into the next of the
+// row's slots from slot0 on (a used slot is written whole, zeros to its end),
+// *acksOut = the ack frames accepted and the row word n | flags is returned.
+// Records past the n-th and slots past the last used one are not written here.
+__device__ __forceinline__ uint32_t ackwalk_row(uint64_t row, uint64_t stride, uint64_t end, uint32_t maxFrames,
+                                                uint32_t ackSlots, uint32_t ackBytes, uint64_t rec, uint64_t slot0,
+                                                uint32_t* acksOut)
 {
-    const uint64_t k = (uint64_t)blockIdx.x * kAckWalkThreads + threadIdx.x;
-    if (k >= count)
-        return;
-    const uint64_t row = rows + k * stride;
-    const uint64_t rec = out + k * maxFrames * 32;
-    const uint64_t slot0 = slots + k * ackSlots * ackBytes;
-    uint64_t end = lens ? lens[k] : stride;
     uint32_t n = 0, acks = 0, flags = 0;
     if (end > stride) {
         flags = kPackedMalformed;
@@ -5024,17 +5024,240 @@ __global__ __launch_bounds__(kAckWalkThreads) void k_ackwalk(uint64_t rows, uint
         ++n;
         at += total;
     }
-    for (uint32_t j = n; j < maxFrames; ++j) {   // every record is written by every scan
+    *acksOut = acks;
+    return n | flags;
+}
+
+__global__ __launch_bounds__(kAckWalkThreads) void k_ackwalk(uint64_t rows, uint64_t stride,
+                                                             const uint32_t* __restrict__ lens, uint32_t count,
+                                                             uint32_t maxFrames, uint32_t ackSlots,
+                                                             uint32_t ackBytes, uint64_t out, uint64_t slots)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kAckWalkThreads + threadIdx.x;
+    if (k >= count)
+        return;
+    const uint64_t rec = out + k * maxFrames * 32;
+    const uint64_t slot0 = slots + k * ackSlots * ackBytes;
+    uint32_t acks = 0;
+    const uint32_t word = ackwalk_row(rows + k * stride, stride, lens ? lens[k] : stride, maxFrames, ackSlots,
+                                      ackBytes, rec, slot0, &acks);
+    for (uint32_t j = word & kPackedCountMask; j < maxFrames; ++j) {   // every record is written by every scan
         st16(rec + (uint64_t)j * 32, make_uint4(0, 0, 0, 0));
         st16(rec + (uint64_t)j * 32 + 16, make_uint4(0, 0, 0, 0));
     }
     for (uint32_t a = acks; a < ackSlots; ++a)   // and every slot
         for (uint32_t o = 0; o < ackBytes; o += 16)
             st16(slot0 + (uint64_t)a * ackBytes + o, make_uint4(0, 0, 0, 0));
-    *reinterpret_cast<GMEM uint32_t*>(out + (uint64_t)count * maxFrames * 32 + k * 4) = n | flags;
+    *reinterpret_cast<GMEM uint32_t*>(out + (uint64_t)count * maxFrames * 32 + k * 4) = word;
     if (k + 1 == count)   // the words between the last row word and the first slot
         for (uint64_t p = out + (uint64_t)count * maxFrames * 32 + (uint64_t)count * 4; p < slots; p += 4)
             *reinterpret_cast<GMEM uint32_t*>(p) = 0;
+}
+
+// ---------------------------------------------------------------------------
+// Dense duplex scan (k_ackwalkd, k_rowsum2, k_compact, k_slots; ops.h
+// duplex_dense_bytes, frames.h duplex_dense_compact is the statement)
+//
+// The dense scan's scheme with the acks' slots as a second compacted list: the
+// walk writes each row's records, slots and ack count into scratch areas that
+// stay on the device, one prefix sum over both counts places them and decides
+// which rows are complete under both budgets, k_compact (unchanged) packs the
+// records and k_slots the slots.
+
+// k_ackwalkd: k_ackwalk's lane per row and ackwalk_row, the records into the
+// row's maxFrames scratch record slots, the messages into its ackSlots scratch
+// message slots (records past the n-th and slots past the last used one stay
+// unwritten: k_compact and k_slots read none of them), the row word into the
+// output's word table and min(acks, ackSlots) into the scratch count table.
+__global__ __launch_bounds__(kAckWalkdThreads) void k_ackwalkd(uint64_t rows, uint64_t stride,
+                                                               const uint32_t* __restrict__ lens, uint32_t count,
+                                                               uint32_t maxFrames, uint32_t ackSlots,
+                                                               uint32_t ackBytes, uint64_t scratchRecs,
+                                                               uint64_t scratchSlots, uint64_t scratchCounts,
+                                                               uint64_t words)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kAckWalkdThreads + threadIdx.x;
+    if (k >= count)
+        return;
+    uint32_t acks = 0;
+    *reinterpret_cast<GMEM uint32_t*>(words + k * 4) =
+        ackwalk_row(rows + k * stride, stride, lens ? lens[k] : stride, maxFrames, ackSlots, ackBytes,
+                    scratchRecs + k * maxFrames * 32, scratchSlots + k * ackSlots * ackBytes, &acks);
+    *reinterpret_cast<GMEM uint32_t*>(scratchCounts + k * 4) = acks < ackSlots ? acks : ackSlots;
+}
+
+// wave_incl_sum on two 32-bit sums at once, the records' in the low half and
+// the acks' in the high half: neither can carry into the other, both totals
+// being below 2^32 (in fact below 2^27: the duplex scan's own size limit)
+__device__ __forceinline__ uint64_t wave_incl_sum2(uint64_t v, uint32_t lane)
+{
+#pragma unroll
+    for (unsigned s = 1; s < 64; s <<= 1) {
+        const uint64_t u = __shfl_up(v, s);
+        if (lane >= s)
+            v += u;
+    }
+    return v;
+}
+
+// k_rowsum2: k_rowsum's carry scheme -- one workgroup striding over the rows,
+// kRowsum2Rows consecutive rows per lane, per pass the lane sums, a wave scan,
+// the wave sums through a double-buffered LDS table behind one barrier, the
+// carry of the passes before in a register -- over the record counts (the row
+// words, clamped to maxFrames) and the ack counts (the scratch count table,
+// clamped to ackSlots) in one pass, so a row's scratch spans can never be left
+// whatever the tables hold.  It writes start[], astart[], the padding behind
+// each and the info words {T, W, c, WA}.  A row is complete while start[k + 1]
+// <= maxRecords and astart[k + 1] <= maxAcks; both sequences only grow, so the
+// number of such rows is c and the largest such starts are W and WA: c is joint
+// over the two tables, which is why this is one kernel and not k_rowsum run
+// twice.  Integers, a fixed order, no atomics.
+__global__ __launch_bounds__(kRowsum2Threads) void k_rowsum2(uint64_t out, uint64_t counts, uint32_t count,
+                                                             uint32_t maxFrames, uint32_t ackSlots,
+                                                             uint32_t maxRecords, uint32_t maxAcks)
+{
+    constexpr uint32_t kWaves = kRowsum2Threads / 64;
+    __shared__ uint64_t wsum[2][kWaves];
+    __shared__ uint32_t redC[kWaves], redW[kWaves], redA[kWaves];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t words = out + 16, starts = words + (uint64_t)count * 4;
+    const uint64_t astarts = out + duplex_dense_acks_offset(count, maxRecords);
+    auto load = [&](uint32_t base, uint64_t* n) {
+        const uint64_t r0 = (uint64_t)base + tid * kRowsum2Rows;
+        uint32_t f[kRowsum2Rows], a[kRowsum2Rows];
+        if (r0 + kRowsum2Rows <= count) {   // (16-byte aligned: base and kRowsum2Rows are multiples of 4)
+            const uint4 x = ld16(words + r0 * 4), y = ld16(words + r0 * 4 + 16);
+            const uint4 p = ld16(counts + r0 * 4), q = ld16(counts + r0 * 4 + 16);
+            f[0] = x.x, f[1] = x.y, f[2] = x.z, f[3] = x.w;
+            f[4] = y.x, f[5] = y.y, f[6] = y.z, f[7] = y.w;
+            a[0] = p.x, a[1] = p.y, a[2] = p.z, a[3] = p.w;
+            a[4] = q.x, a[5] = q.y, a[6] = q.z, a[7] = q.w;
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < kRowsum2Rows; ++j) {
+                const bool in = r0 + j < count;
+                f[j] = in ? *reinterpret_cast<const GMEM uint32_t*>(words + (r0 + j) * 4) : 0u;
+                a[j] = in ? *reinterpret_cast<const GMEM uint32_t*>(counts + (r0 + j) * 4) : 0u;
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kRowsum2Rows; ++j) {
+            f[j] &= kPackedCountMask;
+            f[j] = f[j] < maxFrames ? f[j] : maxFrames;
+            a[j] = a[j] < ackSlots ? a[j] : ackSlots;
+            n[j] = (uint64_t)f[j] | ((uint64_t)a[j] << 32);
+        }
+    };
+    static_assert(kRowsum2Rows == 8, "k_rowsum2 loads a lane's rows as two 16-byte words per table");
+    uint64_t carry = 0;
+    uint32_t done = 0, W = 0, WA = 0;
+    uint64_t nx[kRowsum2Rows];
+    load(0, nx);
+    for (uint32_t base = 0, p = 0; base < count; base += kRowsum2Pass, p ^= 1) {
+        uint64_t n[kRowsum2Rows];
+        uint64_t s = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kRowsum2Rows; ++j) {
+            n[j] = nx[j];
+            s += n[j];
+        }
+        if (count - base > kRowsum2Pass)
+            load(base + kRowsum2Pass, nx);
+        const uint64_t incl = wave_incl_sum2(s, lane);
+        if (lane == 63)
+            wsum[p][wave] = incl;
+        __syncthreads();
+        uint64_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kWaves; ++w) {
+            const uint64_t v = wsum[p][w];
+            total += v;
+            before += w < wave ? v : 0ull;
+        }
+        uint64_t at = carry + before + incl - s;
+        const uint64_t r0 = (uint64_t)base + tid * kRowsum2Rows;
+#pragma unroll
+        for (uint32_t j = 0; j < kRowsum2Rows; ++j) {
+            if (r0 + j < count) {
+                *reinterpret_cast<GMEM uint32_t*>(starts + (r0 + j) * 4) = (uint32_t)at;
+                *reinterpret_cast<GMEM uint32_t*>(astarts + (r0 + j) * 4) = (uint32_t)(at >> 32);
+                at += n[j];
+                if ((uint32_t)at <= maxRecords && (uint32_t)(at >> 32) <= maxAcks) {
+                    ++done;
+                    W = (uint32_t)at;
+                    WA = (uint32_t)(at >> 32);
+                }
+            }
+        }
+        carry += total;
+    }
+    // c = the sum of done, W and WA = the largest ones (0 where no row is complete)
+#pragma unroll
+    for (unsigned s = 32; s >= 1; s >>= 1) {
+        done += __shfl_xor(done, s);
+        const uint32_t o = __shfl_xor(W, s), oa = __shfl_xor(WA, s);
+        W = W > o ? W : o;
+        WA = WA > oa ? WA : oa;
+    }
+    if (lane == 0) {
+        redC[wave] = done;
+        redW[wave] = W;
+        redA[wave] = WA;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t c = 0, w = 0, wa = 0;
+        for (uint32_t i = 0; i < kWaves; ++i) {
+            c += redC[i];
+            w = w > redW[i] ? w : redW[i];
+            wa = wa > redA[i] ? wa : redA[i];
+        }
+        *reinterpret_cast<GMEM uint32_t*>(starts + (uint64_t)count * 4) = (uint32_t)carry;
+        for (uint64_t a = starts + (uint64_t)(count + 1) * 4; a < out + dense_records_offset(count); a += 4)
+            *reinterpret_cast<GMEM uint32_t*>(a) = 0;
+        *reinterpret_cast<GMEM uint32_t*>(astarts + (uint64_t)count * 4) = (uint32_t)(carry >> 32);
+        for (uint64_t a = astarts + (uint64_t)(count + 1) * 4; a < out + duplex_dense_slots_offset(count, maxRecords);
+             a += 4)
+            *reinterpret_cast<GMEM uint32_t*>(a) = 0;
+        st16(out, make_uint4((uint32_t)carry, w, c, wa));
+    }
+}
+
+// k_slots: one 16-byte word of the output's slot area per lane, over all
+// maxAcks * ackBytes / 16 words: a wave stores 1 KiB of consecutive bytes.
+// Slot i < WA belongs to the row k with astart[k] <= i < astart[k + 1] (rows
+// without a slot share a start with the next row and own none): a binary search
+// over astart[0, c], whose two ends hold 0 and WA, so k < c always; the table
+// stays in cache.  The word comes from slot i - astart[k] of row k's scratch
+// slots (below ackSlots, by k_rowsum2's clamp); a word from WA on is zero.  No
+// LDS, no atomics.
+__global__ __launch_bounds__(kSlotsThreads) void k_slots(uint64_t out, uint64_t scratchSlots, uint32_t count,
+                                                         uint32_t ackSlots, uint32_t ackBytes, uint32_t maxRecords,
+                                                         uint32_t maxAcks)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * kSlotsThreads + threadIdx.x;
+    const uint32_t per = ackBytes >> 4;   // 16-byte words per slot
+    if (g >= (uint64_t)maxAcks * per)
+        return;
+    const uint64_t i = g / per, o = (g - i * per) * 16;
+    const uint4 info = ld16(out);   // {T, W, c, WA}
+    const uint32_t c = info.z < count ? info.z : count;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (i < info.w && c != 0) {
+        const uint64_t astarts = out + duplex_dense_acks_offset(count, maxRecords);
+        uint32_t lo = 0, hi = c;   // astart[lo] <= i < astart[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (*reinterpret_cast<const GMEM uint32_t*>(astarts + (uint64_t)mid * 4) <= i)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const uint64_t j = i - *reinterpret_cast<const GMEM uint32_t*>(astarts + (uint64_t)lo * 4);
+        if (j < ackSlots)
+            v = ld16(scratchSlots + ((uint64_t)lo * ackSlots + j) * ackBytes + o);
+    }
+    st16(out + duplex_dense_slots_offset(count, maxRecords) + g * 16, v);
 }
 
 // ---------------------------------------------------------------------------
@@ -5138,7 +5361,7 @@ void harvest_timing(bool all)
             break;
         // (a synchronised codec stream says nothing about the gather stream)
         if (all && (ev.kind == kBeScan || ev.kind == kBeWalk || ev.kind == kBeAckWalk || ev.kind == kBeRowsum ||
-                    ev.kind == kBeCompact))
+                    ev.kind == kBeCompact || ev.kind == kBeRowsum2 || ev.kind == kBeSlots))
             (void)hipEventSynchronize(ev.b);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.a, ev.b);
@@ -6146,6 +6369,61 @@ bool be_ackwalk_rows(const void* rows, uint64_t stride, const uint32_t* lens, ui
         return false;
     *packed = p;
     if (hipMemcpyAsync(hostOut, devStage, (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes),
+                       hipMemcpyDeviceToHost, g_gatherStream) != hipSuccess ||
+        hipEventRecord(l, g_gatherStream) != hipSuccess) {
+        be_mark_release(l);
+        return false;
+    }
+    *landed = l;
+    return true;
+}
+
+bool be_duplex_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count,
+                          uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes, uint32_t maxRecords,
+                          uint32_t maxAcks, void* devStage, void* hostOut, void** packed, void** landed)
+{
+    bind_device();
+    *packed = *landed = nullptr;
+    hipEvent_t p = take_mark(), l = take_mark();
+    if (!p || !l) {
+        be_mark_release(p);
+        be_mark_release(l);
+        return false;
+    }
+    const uint64_t out = (uint64_t)(uintptr_t)devStage;
+    const uint64_t recs = out + duplex_dense_scratch_records(count, maxRecords, maxAcks, ackBytes);
+    const uint64_t slots = out + duplex_dense_scratch_slots(count, maxFrames, maxRecords, maxAcks, ackBytes);
+    const uint64_t counts =
+        out + duplex_dense_scratch_counts(count, maxFrames, ackSlots, maxRecords, maxAcks, ackBytes);
+    {
+        Timed t(kBeAckWalk, g_gatherStream);
+        hipLaunchKernelGGL(k_ackwalkd, dim3((count + kAckWalkdThreads - 1) / kAckWalkdThreads),
+                           dim3(kAckWalkdThreads), 0, g_gatherStream, (uint64_t)(uintptr_t)rows, stride, lens, count,
+                           maxFrames, ackSlots, ackBytes, recs, slots, counts, out + 16);
+    }
+    // (the rows have been read: what follows works on the staging area alone)
+    if (hipEventRecord(p, g_gatherStream) != hipSuccess)
+        return false;
+    *packed = p;
+    {
+        Timed t(kBeRowsum2, g_gatherStream);
+        hipLaunchKernelGGL(k_rowsum2, dim3(1), dim3(kRowsum2Threads), 0, g_gatherStream, out, counts, count,
+                           maxFrames, ackSlots, maxRecords, maxAcks);
+    }
+    {
+        Timed t(kBeCompact, g_gatherStream);
+        const uint64_t lanes = 2 * (uint64_t)maxRecords;
+        hipLaunchKernelGGL(k_compact, dim3((uint32_t)((lanes + kCompactThreads - 1) / kCompactThreads)),
+                           dim3(kCompactThreads), 0, g_gatherStream, out, recs, count, maxFrames, maxRecords);
+    }
+    {
+        Timed t(kBeSlots, g_gatherStream);
+        const uint64_t lanes = (uint64_t)maxAcks * (ackBytes >> 4);
+        hipLaunchKernelGGL(k_slots, dim3((uint32_t)((lanes + kSlotsThreads - 1) / kSlotsThreads)),
+                           dim3(kSlotsThreads), 0, g_gatherStream, out, slots, count, ackSlots, ackBytes, maxRecords,
+                           maxAcks);
+    }
+    if (hipMemcpyAsync(hostOut, devStage, (size_t)duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes),
                        hipMemcpyDeviceToHost, g_gatherStream) != hipSuccess ||
         hipEventRecord(l, g_gatherStream) != hipSuccess) {
         be_mark_release(l);

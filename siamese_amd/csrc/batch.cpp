@@ -1113,6 +1113,46 @@ inline bool duplex_ok(unsigned maxFrames, unsigned ackSlots, unsigned ackBytes)
     return maxFrames >= 1 && maxFrames <= kPackedMaxFrames && ackSlots >= 1 && ackSlots <= maxFrames &&
            ackBytes >= kAckSlotBytesMin && ackBytes <= kAckSlotBytesMax && (ackBytes & 15u) == 0;
 }
+
+// One record of a duplex scan's row, copied from the caller's memory, for sgpu_frames_recv_duplex and
+// sgpu_frames_recv_duplex_dense: an ack goes from its slot to encoders[Flow], anything else to
+// decoders[Flow].  acks = the ack records met in this row before this one (counted here); rowSlots = the
+// row's slot 0, of which rowSlotCount slots may be read; rowDev = the row's device address.
+inline SiameseResult route_duplex_head(const SgpuDecoder* decoders, unsigned decoderCount,
+                                       const SgpuEncoder* encoders, unsigned encoderCount, const PackedHead& h,
+                                       uint64_t stride, unsigned ackSlots, unsigned ackBytes, unsigned& acks,
+                                       const uint8_t* rowSlots, unsigned rowSlotCount, uint64_t rowDev,
+                                       unsigned* nextOut, unsigned* accepted)
+{
+    SiameseResult r = Siamese_InvalidInput;
+    if (h.type == kFrameAck) {
+        // a truncated message is never handed on: cut short it states another loss list
+        SgpuEncoder e = h.flow < encoderCount ? encoders[h.flow] : nullptr;
+        if (ack_head_valid(h, stride, ackSlots, ackBytes, acks) && h.status == kRowOk && h.packetNum < rowSlotCount &&
+            e) {
+            uint8_t msg[kAckSlotBytesMax];
+            std::memcpy(msg, rowSlots + (size_t)h.packetNum * ackBytes, h.dataBytes);
+            unsigned next = 0;
+            r = BE(e)->core.acknowledge(msg, h.dataBytes, next);
+            if (nextOut)
+                *nextOut = next;
+            ++*accepted;
+        }
+        ++acks;
+    } else if (packed_head_valid(h, stride))
+        r = route_head(decoders, decoderCount, h, rowDev + h.offset + h.headerBytes, accepted);
+    return r;
+}
+
+// the sizes sgpu_frames_scan_duplex_dense and sgpu_frames_recv_duplex_dense share
+inline bool duplex_dense_ok(unsigned count, unsigned maxFrames, unsigned ackSlots, unsigned ackBytes,
+                            unsigned maxRecords, unsigned maxAcks)
+{
+    return duplex_ok(maxFrames, ackSlots, ackBytes) && maxRecords >= maxFrames &&
+           (uint64_t)maxRecords <= (uint64_t)count * maxFrames && maxAcks >= ackSlots &&
+           (uint64_t)maxAcks <= (uint64_t)count * ackSlots &&
+           duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes) < ((uint64_t)1 << 32);
+}
 } // namespace
 
 SIAMESE_EXPORT size_t sgpu_frames_duplex_bytes(unsigned count, unsigned maxFrames, unsigned ackSlots,
@@ -1174,23 +1214,10 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex(const SgpuDecoder* decoders
         for (unsigned j = 0; j < n; ++j) {
             PackedHead h;
             std::memcpy(&h, recs + ((size_t)k * maxFrames + j) * sizeof(h), sizeof(h));
-            SiameseResult r = Siamese_InvalidInput;
-            if (h.type == kFrameAck) {
-                // a truncated message is never handed on: cut short it states another loss list
-                SgpuEncoder e = h.flow < encoderCount ? encoders[h.flow] : nullptr;
-                if (ack_head_valid(h, stride, ackSlots, ackBytes, acks) && h.status == kRowOk && e) {
-                    uint8_t msg[kAckSlotBytesMax];
-                    std::memcpy(msg, slots + ((size_t)k * ackSlots + h.packetNum) * ackBytes, h.dataBytes);
-                    unsigned next = 0;
-                    r = BE(e)->core.acknowledge(msg, h.dataBytes, next);
-                    if (nextExpectedOut)
-                        nextExpectedOut[(size_t)k * maxFrames + j] = next;
-                    ++accepted;
-                }
-                ++acks;
-            } else if (packed_head_valid(h, stride))
-                r = route_head(decoders, decoderCount, h, dev + (uint64_t)k * stride + h.offset + h.headerBytes,
-                               &accepted);
+            const SiameseResult r = route_duplex_head(
+                decoders, decoderCount, encoders, encoderCount, h, stride, ackSlots, ackBytes, acks,
+                slots + (size_t)k * ackSlots * ackBytes, ackSlots, dev + (uint64_t)k * stride,
+                nextExpectedOut ? nextExpectedOut + (size_t)k * maxFrames + j : nullptr, &accepted);
             if (res)
                 res[j] = r;
             if (r != Siamese_Success && r != Siamese_NeedMoreData && status == Siamese_Success)
@@ -1205,6 +1232,143 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex(const SgpuDecoder* decoders
     }
     *acceptedOut = accepted;
     return status;
+}
+
+SIAMESE_EXPORT size_t sgpu_frames_duplex_dense_bytes(unsigned count, unsigned maxRecords, unsigned maxAcks,
+                                                     unsigned ackBytes)
+{
+    // (what no maxFrames and ackSlots allow: fewer than one record or slot, more than 256 per row)
+    if (maxRecords < 1 || (uint64_t)maxRecords > (uint64_t)count * kPackedMaxFrames || maxAcks < 1 ||
+        (uint64_t)maxAcks > (uint64_t)count * kPackedMaxFrames || !duplex_ok(1, 1, ackBytes) ||
+        duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes) >= ((uint64_t)1 << 32))
+        return 0;
+    return (size_t)duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes);
+}
+
+SIAMESE_EXPORT size_t sgpu_frames_duplex_dense_acks(unsigned count, unsigned maxRecords)
+{
+    return maxRecords >= 1 && (uint64_t)maxRecords <= (uint64_t)count * kPackedMaxFrames
+               ? (size_t)duplex_dense_acks_offset(count, maxRecords)
+               : 0;
+}
+
+SIAMESE_EXPORT size_t sgpu_frames_duplex_dense_slots(unsigned count, unsigned maxRecords)
+{
+    return maxRecords >= 1 && (uint64_t)maxRecords <= (uint64_t)count * kPackedMaxFrames
+               ? (size_t)duplex_dense_slots_offset(count, maxRecords)
+               : 0;
+}
+
+SIAMESE_EXPORT long long sgpu_frames_scan_duplex_dense(const void* deviceRows, size_t stride,
+                                                       const unsigned* deviceLens, unsigned count,
+                                                       unsigned maxFrames, unsigned ackSlots, unsigned ackBytes,
+                                                       unsigned maxRecords, unsigned maxAcks, void* pinnedOut)
+{
+    if (!g_batchReady || !rows_ok(deviceRows, stride, count) || ((uintptr_t)deviceLens & 3) ||
+        ((uintptr_t)pinnedOut & 15) || (!pinnedOut && count > 0) || !duplex_ok(maxFrames, ackSlots, ackBytes) ||
+        duplex_bytes(count, maxFrames, ackSlots, ackBytes) > ((uint64_t)1 << 32))
+        return -1;
+    // (count == 0 admits no maxRecords >= maxFrames: its ticket is complete and nothing is written)
+    if (count > 0 && !duplex_dense_ok(count, maxFrames, ackSlots, ackBytes, maxRecords, maxAcks))
+        return -1;
+    return (long long)Engine::global()->duplex_dense_rows_async(deviceRows, stride, deviceLens, count, maxFrames,
+                                                                ackSlots, ackBytes, count ? maxRecords : 0,
+                                                                count ? maxAcks : 0, pinnedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                           const SgpuEncoder* encoders, unsigned encoderCount,
+                                                           const void* heads, unsigned maxFrames, unsigned ackSlots,
+                                                           unsigned ackBytes, unsigned maxRecords, unsigned maxAcks,
+                                                           const void* deviceRows, size_t stride, unsigned count,
+                                                           SiameseResult* results, unsigned* nextExpectedOut,
+                                                           unsigned* rowsOut, unsigned* acceptedOut)
+{
+    if (rowsOut)
+        *rowsOut = 0;
+    if (!acceptedOut)
+        return Siamese_InvalidInput;
+    *acceptedOut = 0;
+    if (!rowsOut || !rows_ok(deviceRows, stride, count) || (!heads && count > 0) || (!decoders && decoderCount) ||
+        (!encoders && encoderCount) || ((uintptr_t)heads & 3) || !duplex_ok(maxFrames, ackSlots, ackBytes) ||
+        (count > 0 && !duplex_dense_ok(count, maxFrames, ackSlots, ackBytes, maxRecords, maxAcks)))
+        return Siamese_InvalidInput;
+    if (count == 0)
+        return Siamese_Success;
+    for (unsigned i = 0; results && i < maxRecords; ++i)
+        results[i] = Siamese_NeedMoreData;
+    // (the output is the caller's memory: every word, record and slot is copied, checked and only then used)
+    const uint64_t dev = (uint64_t)(uintptr_t)deviceRows;
+    const uint8_t* base = static_cast<const uint8_t*>(heads);
+    const uint8_t* words = base + 16;
+    const uint8_t* starts = words + (size_t)count * 4;
+    const uint8_t* recs = base + (size_t)dense_records_offset(count);
+    const uint8_t* astarts = base + (size_t)duplex_dense_acks_offset(count, maxRecords);
+    const uint8_t* slots = base + (size_t)duplex_dense_slots_offset(count, maxRecords);
+    uint32_t info[4];
+    std::memcpy(info, base, sizeof(info));
+    const uint32_t W = info[1], c = info[2], WA = info[3];
+    if (c > count || W > maxRecords || WA > maxAcks)
+        return Siamese_InvalidInput;
+    unsigned accepted = 0;
+    SiameseResult status = Siamese_Success;
+    uint32_t at = 0, aat = 0;   // start[k] and astart[k], checked
+    std::memcpy(&at, starts, 4);
+    std::memcpy(&aat, astarts, 4);
+    bool forged = at != 0 || aat != 0;
+    unsigned k = 0;
+    for (; !forged && k < c; ++k) {
+        uint32_t word, next, anext;
+        std::memcpy(&word, words + (size_t)k * 4, 4);
+        std::memcpy(&next, starts + (size_t)(k + 1) * 4, 4);
+        std::memcpy(&anext, astarts + (size_t)(k + 1) * 4, 4);
+        unsigned n = word & kPackedCountMask;
+        bool malformed = (word & kPackedMalformed) != 0;
+        const unsigned span = n < maxFrames ? n : maxFrames;
+        // the row's records are [at, next): non-decreasing, as many as its word says, and before W
+        if (next < at || next - at != span || next > W) {
+            forged = true;
+            break;
+        }
+        // the row's slots are [aat, anext): non-decreasing, one for each of its ack records that names a
+        // slot, and before WA
+        unsigned named = 0;
+        for (unsigned j = 0; j < span; ++j) {
+            PackedHead h;
+            std::memcpy(&h, recs + ((size_t)at + j) * sizeof(h), sizeof(h));
+            named += h.type == kFrameAck && h.packetNum < ackSlots;
+        }
+        if (anext < aat || anext - aat != named || anext > WA) {
+            forged = true;
+            break;
+        }
+        if (n > maxFrames) {   // (no scan writes such a word: none of the row's records is used)
+            n = 0;
+            malformed = true;
+        }
+        unsigned acks = 0;   // ack records met in this row
+        for (unsigned j = 0; j < n; ++j) {
+            PackedHead h;
+            std::memcpy(&h, recs + ((size_t)at + j) * sizeof(h), sizeof(h));
+            const SiameseResult r = route_duplex_head(
+                decoders, decoderCount, encoders, encoderCount, h, stride, ackSlots, ackBytes, acks,
+                slots + (size_t)aat * ackBytes, named, dev + (uint64_t)k * stride,
+                nextExpectedOut ? nextExpectedOut + at + j : nullptr, &accepted);
+            if (results)
+                results[at + j] = r;
+            if (r != Siamese_Success && r != Siamese_NeedMoreData && status == Siamese_Success)
+                status = r;
+        }
+        if (malformed && status == Siamese_Success)   // (the frame the walk stopped at has no slot here)
+            status = Siamese_InvalidInput;
+        at = next;
+        aat = anext;
+    }
+    if (!forged && (at != W || aat != WA))
+        forged = true;
+    *rowsOut = k;   // c, unless a table stopped the routing before it
+    *acceptedOut = accepted;
+    return forged ? Siamese_InvalidInput : status;
 }
 
 SIAMESE_EXPORT long long sgpu_frames_send(unsigned count, const SgpuRecoveryPacket* packets, const unsigned* flows,
@@ -1256,7 +1420,7 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
     const Engine* e = Engine::global();
-    const uint64_t v[39] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[40] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
@@ -1267,8 +1431,9 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
                             Engine::global()->concats(),
                             e->rows_shape(0), e->rows_shape(1), e->rows_shape(2), e->rows_shape(3),
                             e->rows_shape(4), be_exec_stage_cap(),
-                            e->denses(),  s.gePivoted,   s.geSingular};
-    for (unsigned k = 0; k < count && k < 39; ++k)
+                            e->denses(),  s.gePivoted,   s.geSingular,
+                            e->duplex_denses()};
+    for (unsigned k = 0; k < count && k < 40; ++k)
         out[k] = v[k];
 }
 

@@ -3167,10 +3167,11 @@ int64_t Engine::gather_async_framed(unsigned count, const void* const* srcs, con
 
 // scan_rows_async (maxFrames == 0: k_scan) and walk_rows_async (k_walk)
 // and duplex_rows_async (ackSlots != 0: k_ackwalk) and dense_rows_async
-// (maxRecords != 0: k_walkd, k_rowsum and k_compact)
+// (maxRecords != 0: k_walkd, k_rowsum and k_compact) and duplex_dense_rows_async (maxRecords != 0 and
+// ackSlots != 0: k_ackwalkd, k_rowsum2, k_compact and k_slots)
 int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
                            unsigned maxFrames, void* pinnedOut, unsigned ackSlots, unsigned ackBytes,
-                           unsigned maxRecords)
+                           unsigned maxRecords, unsigned maxAcks)
 {
     if (failed())
         return -1;
@@ -3181,9 +3182,12 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     GatherSlot& g = gslots_[ticket % kGatherSlots];
     if (!gather_land(g))   // (the slot's previous gather, kGatherSlots back)
         return -1;
-    // the records take the slot's packing area (the dense scan's scratch records behind its output); a scan
+    // the records take the slot's packing area (the dense scans' scratch areas behind their output); a scan
     // uploads no descriptors
-    const size_t total = maxRecords  ? (size_t)dense_stage_bytes(count, maxFrames, maxRecords)
+    const bool duplexDense = maxRecords && ackSlots;
+    const size_t total = duplexDense ? (size_t)duplex_dense_stage_bytes(count, maxFrames, ackSlots, maxRecords,
+                                                                        maxAcks, ackBytes)
+                         : maxRecords ? (size_t)dense_stage_bytes(count, maxFrames, maxRecords)
                          : ackSlots  ? (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes)
                          : maxFrames ? (size_t)packed_bytes(count, maxFrames)
                                      : (size_t)count * sizeof(RowHead);
@@ -3199,7 +3203,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     if (!g.stage)
         return -1;
     void* packed = nullptr;
-    if (!(maxRecords  ? be_dense_rows(rows, stride, lens, count, maxFrames, maxRecords, g.stage, pinnedOut, &packed,
+    if (!(duplexDense ? be_duplex_dense_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, maxRecords,
+                                             maxAcks, g.stage, pinnedOut, &packed, &g.landed)
+          : maxRecords ? be_dense_rows(rows, stride, lens, count, maxFrames, maxRecords, g.stage, pinnedOut, &packed,
                                       &g.landed)
           : ackSlots  ? be_ackwalk_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, g.stage, pinnedOut,
                                         &packed, &g.landed)
@@ -3209,7 +3215,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
         return -1;
     }
     g.ticket = ticket;
-    if (maxRecords)
+    if (duplexDense)
+        duplexDenses_.fetch_add(count, std::memory_order_relaxed);
+    else if (maxRecords)
         denses_.fetch_add(count, std::memory_order_relaxed);
     else if (ackSlots)
         duplexes_.fetch_add(count, std::memory_order_relaxed);

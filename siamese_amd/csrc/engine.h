@@ -799,6 +799,20 @@ public:
     {
         return rows_async(rows, stride, lens, count, maxFrames, pinnedOut, 0, 0, maxRecords);
     }
+    /// The duplex scan in that dense form: the records back to back and, behind
+    /// a second table of per-row starts, the acks' slots back to back,
+    /// duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes) in all, into
+    /// pinnedOut (k_ackwalkd, k_rowsum2, k_compact and k_slots,
+    /// sgpu_frames_scan_duplex_dense).  maxFrames <= maxRecords <= count *
+    /// maxFrames and ackSlots <= maxAcks <= count * ackSlots.  The same gather
+    /// slots and tickets; the slot's staging area also holds the walk's per-row
+    /// scratch records, slots and ack counts, which stay on the device.
+    int64_t duplex_dense_rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
+                                    unsigned maxFrames, unsigned ackSlots, unsigned ackBytes, unsigned maxRecords,
+                                    unsigned maxAcks, void* pinnedOut)
+    {
+        return rows_async(rows, stride, lens, count, maxFrames, pinnedOut, ackSlots, ackBytes, maxRecords, maxAcks);
+    }
     /// Wait until gather `ticket` and every earlier one have landed.
     bool gather_wait(int64_t ticket);
     /// Host -> device copy on the staging stream, issued now; every later
@@ -972,7 +986,8 @@ private:
     int64_t gNext_ = 0;
     bool gather_land(GatherSlot& g);
     int64_t rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count, unsigned maxFrames,
-                       void* pinnedOut, unsigned ackSlots = 0, unsigned ackBytes = 0, unsigned maxRecords = 0);
+                       void* pinnedOut, unsigned ackSlots = 0, unsigned ackBytes = 0, unsigned maxRecords = 0,
+                       unsigned maxAcks = 0);
     // rows scanned by the packed scan, counted when the scan is queued (sgpu_engine_stats_ex [24]); kept
     // here, behind every other member, and not in EngineStats, whose size every submission's counters share
     std::atomic<uint64_t> walks_{0};
@@ -994,6 +1009,9 @@ private:
     // for the same reason
     static constexpr unsigned kRowsShapeStats = 5;
     std::atomic<uint64_t> rowsShape_[kRowsShapeStats] = {};
+    // rows scanned by the duplex dense scan, counted as walks_ ([39]); behind every other member, so that
+    // none of them moves
+    std::atomic<uint64_t> duplexDenses_{0};
 
 public:
     uint64_t rows_shape(unsigned k) const { return rowsShape_[k].load(std::memory_order_relaxed); }
@@ -1001,6 +1019,7 @@ public:
     uint64_t packs() const { return packs_.load(std::memory_order_relaxed); }
     uint64_t concats() const { return concats_.load(std::memory_order_relaxed); }
     uint64_t denses() const { return denses_.load(std::memory_order_relaxed); }
+    uint64_t duplex_denses() const { return duplexDenses_.load(std::memory_order_relaxed); }
     uint64_t duplexes() const { return duplexes_.load(std::memory_order_relaxed); }
     uint64_t ack_frames() const { return ackFrames_.load(std::memory_order_relaxed); }
     void count_ack_frames(uint64_t n) { ackFrames_.fetch_add(n, std::memory_order_relaxed); }

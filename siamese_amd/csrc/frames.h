@@ -394,6 +394,63 @@ inline uint32_t ack_walk(const uint8_t* row, uint64_t stride, const uint32_t* le
     return n | flags;
 }
 
+/// What k_rowsum2, k_compact and k_slots compute from ack_walk's output (ops.h
+/// duplex_dense_bytes states the layout, sgpu_frames_scan_duplex_dense /
+/// sgpu_frames_recv_duplex_dense use it): words = the count row words, rowRecs =
+/// maxFrames records per row and rowSlots = ackSlots slots of ackBytes bytes per
+/// row as ack_walk writes them, out = duplex_dense_bytes(count, maxRecords,
+/// maxAcks, ackBytes) bytes, every one of which is written.  Row k's share of
+/// the slots is a_k = the ack records among its first n_k, at most ackSlots
+/// (n_k clamped to maxFrames as in dense_compact).  start[] and astart[] are the
+/// exclusive prefix sums of n_k and a_k; rows are all or nothing over both
+/// budgets: c is the largest value with start[c] <= maxRecords and astart[c] <=
+/// maxAcks, the records and slots of rows [0, c) lie back to back from record 0
+/// and slot 0, and records from W = start[c] and slots from WA = astart[c] on
+/// are zero.
+inline void duplex_dense_compact(const uint32_t* words, const PackedHead* rowRecs, const uint8_t* rowSlots,
+                                 uint32_t count, uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes,
+                                 uint32_t maxRecords, uint32_t maxAcks, uint8_t* out)
+{
+    const size_t recAt = (size_t)dense_records_offset(count);
+    const size_t slotAt = (size_t)duplex_dense_slots_offset(count, maxRecords);
+    std::memset(out, 0, (size_t)duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes));
+    uint8_t* wordsOut = out + 16;
+    uint8_t* starts = wordsOut + (size_t)count * 4;
+    uint8_t* astarts = out + (size_t)duplex_dense_acks_offset(count, maxRecords);
+    uint32_t sum = 0, asum = 0, c = 0, W = 0, WA = 0;
+    bool open = true;   // (both sums only grow: a row that does not fit closes the prefix)
+    for (uint32_t k = 0; k < count; ++k) {
+        const uint32_t w = words[k];
+        uint32_t n = w & kPackedCountMask;
+        if (n > maxFrames)
+            n = maxFrames;
+        uint32_t a = 0;
+        for (uint32_t j = 0; j < n; ++j)
+            a += rowRecs[(size_t)k * maxFrames + j].type == kFrameAck;
+        if (a > ackSlots)
+            a = ackSlots;
+        std::memcpy(wordsOut + (size_t)k * 4, &w, 4);
+        std::memcpy(starts + (size_t)k * 4, &sum, 4);
+        std::memcpy(astarts + (size_t)k * 4, &asum, 4);
+        open = open && (uint64_t)sum + n <= maxRecords && (uint64_t)asum + a <= maxAcks;
+        if (open) {
+            std::memcpy(out + recAt + (size_t)sum * sizeof(PackedHead), rowRecs + (size_t)k * maxFrames,
+                        (size_t)n * sizeof(PackedHead));
+            std::memcpy(out + slotAt + (size_t)asum * ackBytes, rowSlots + (size_t)k * ackSlots * ackBytes,
+                        (size_t)a * ackBytes);
+            c = k + 1;
+            W = sum + n;
+            WA = asum + a;
+        }
+        sum += n;
+        asum += a;
+    }
+    std::memcpy(starts + (size_t)count * 4, &sum, 4);
+    std::memcpy(astarts + (size_t)count * 4, &asum, 4);
+    const uint32_t info[4] = {sum, W, c, WA};
+    std::memcpy(out, info, 16);
+}
+
 /// What k_relay computes for one present item (ops.h RelayItem): the symbol
 /// sym, of which cap bytes may be read, as the wire frame of original
 /// packetNum of `flow` in row[0, stride), its length in *len.  With hs and n

@@ -714,6 +714,71 @@ constexpr uint64_t dense_stage_bytes(uint64_t count, uint64_t maxFrames, uint64_
     return dense_scratch_offset(count, maxRecords) + count * maxFrames * sizeof(PackedHead);
 }
 
+/// The duplex scan in dense form (k_ackwalkd, k_rowsum2, k_compact and k_slots,
+/// sgpu_frames_scan_duplex_dense): the dense layout above with info word 3 =
+/// WA, and behind the records a second table and the acks' message slots back
+/// to back.  The output is
+///   info {T, W, c, WA} | count row words | count + 1 start words | zeros to the
+///   next 16-byte boundary | maxRecords PackedHead records | count + 1 ack start
+///   words | zeros to the next 16-byte boundary | maxAcks slots of ackBytes
+/// where row word k is k_ackwalk's, a_k = min(ack frames of row k, ackSlots),
+/// astart[0] = 0 and astart[k + 1] = astart[k] + a_k.  Rows are all or nothing
+/// over both budgets: c is the largest value with start[c] <= maxRecords and
+/// astart[c] <= maxAcks, W = start[c], WA = astart[c].  Slot astart[k] + a, for
+/// k < c and a < a_k, is row k's slot a as k_ackwalk writes it; slots [WA,
+/// maxAcks) are zero (frames.h duplex_dense_compact states all of it).
+/// ackSlots <= maxAcks <= count * ackSlots.
+///
+/// On the device the walk writes into scratch areas behind the output, none of
+/// which crosses to the host: count * maxFrames records, count * ackSlots slots
+/// and count ack counts.  Every offset below is a multiple of 16.  k_ackwalkd
+/// takes one lane per row, kAckWalkdThreads rows per workgroup; k_rowsum2 is
+/// k_rowsum's single striding workgroup (kRowsum2Threads lanes, kRowsum2Rows
+/// consecutive rows per lane, kRowsum2Pass rows per pass) over both counts at
+/// once; k_slots takes one 16-byte word of the slot area per lane, kSlotsThreads
+/// lanes per workgroup.
+constexpr uint32_t kAckWalkdThreads = 256;
+constexpr uint32_t kRowsum2Threads = 1024;
+constexpr uint32_t kRowsum2Rows = 8;
+constexpr uint32_t kRowsum2Pass = kRowsum2Threads * kRowsum2Rows;
+constexpr uint32_t kSlotsThreads = 256;
+/// Where a duplex dense scan's ack starts and slots begin, and its output's bytes.
+constexpr uint64_t duplex_dense_acks_offset(uint64_t count, uint64_t maxRecords)
+{
+    return dense_bytes(count, maxRecords);   // (a multiple of 16)
+}
+constexpr uint64_t duplex_dense_slots_offset(uint64_t count, uint64_t maxRecords)
+{
+    return duplex_dense_acks_offset(count, maxRecords) + (((count + 1) * 4 + 15) & ~(uint64_t)15);
+}
+constexpr uint64_t duplex_dense_bytes(uint64_t count, uint64_t maxRecords, uint64_t maxAcks, uint64_t ackBytes)
+{
+    return duplex_dense_slots_offset(count, maxRecords) + maxAcks * ackBytes;   // (ackBytes: a multiple of 16)
+}
+/// The device's scratch areas in the staging area: the rows' records, the rows'
+/// slots, the rows' ack counts (rounded up to whole 16-byte words).
+constexpr uint64_t duplex_dense_scratch_records(uint64_t count, uint64_t maxRecords, uint64_t maxAcks,
+                                                uint64_t ackBytes)
+{
+    return duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes);
+}
+constexpr uint64_t duplex_dense_scratch_slots(uint64_t count, uint64_t maxFrames, uint64_t maxRecords,
+                                              uint64_t maxAcks, uint64_t ackBytes)
+{
+    return duplex_dense_scratch_records(count, maxRecords, maxAcks, ackBytes) + count * maxFrames * sizeof(PackedHead);
+}
+constexpr uint64_t duplex_dense_scratch_counts(uint64_t count, uint64_t maxFrames, uint64_t ackSlots,
+                                               uint64_t maxRecords, uint64_t maxAcks, uint64_t ackBytes)
+{
+    return duplex_dense_scratch_slots(count, maxFrames, maxRecords, maxAcks, ackBytes) + count * ackSlots * ackBytes;
+}
+constexpr uint64_t duplex_dense_stage_bytes(uint64_t count, uint64_t maxFrames, uint64_t ackSlots,
+                                            uint64_t maxRecords, uint64_t maxAcks, uint64_t ackBytes)
+{
+    return duplex_dense_scratch_counts(count, maxFrames, ackSlots, maxRecords, maxAcks, ackBytes) +
+           ((count * 4 + 15) & ~(uint64_t)15);
+}
+
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)
 /// Solves with more rows than this stage 256-byte tiles (16 lanes x 16 bytes

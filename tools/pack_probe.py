@@ -36,7 +36,24 @@ both with maxFrames = --frames, interleaved in the same process:
 For each: the bytes to the host, the median and range of scan plus wait, and
 the device time of each kernel (sgpu_timing_kernels [8], [15], [16]).
 
-    python tools/pack_probe.py [--flows 1024] [--rows 320] [--frames 8] [--reps 9] [--dense] [--out FILE]
+--duplex-dense adds two legs that compare sgpu_frames_scan_duplex with
+sgpu_frames_scan_duplex_dense (k_ackwalk's walk, k_rowsum2, k_compact, k_slots)
+on the same rows, both with maxFrames = --frames + 1, ackSlots 1 and ackBytes
+64, interleaved in the same process.  Every row is built with an 8-byte
+acknowledgement frame behind its last frame, which the length words of the legs
+above hide:
+
+  all-full    every row full and its ack in every row: maxRecords = rows x
+              (frames + 1) and maxAcks = rows, where the dense form cannot win;
+  mixed-fill  the mixed-fill rows above, and in one row of 16 an ack written
+              behind the row's last frame: maxRecords and maxAcks = the known
+              totals rounded up to a multiple of 1024.
+
+For each: the bytes to the host, the median and range of scan plus wait, and
+the device time of each kernel (sgpu_timing_kernels [12], [17], [16], [18]).
+
+    python tools/pack_probe.py [--flows 1024] [--rows 320] [--frames 8] [--reps 9] [--dense] [--duplex-dense]
+                               [--out FILE]
 
 Needs an MI355X: without one the library refuses to initialise and the probe
 fails (no CPU fallback; --library with the CPU test double rehearses the call
@@ -125,6 +142,93 @@ def dense_legs(L, a, dev, lens, rows, nf, stride, ends, rehearsal):
     return legs
 
 
+ACK_MSG = bytes(range(0xA0, 0xA8))   # the probe's 8-byte acknowledgement message
+ACK_EVERY = 16                        # the mixed-fill leg: an ack in one row of this many
+
+
+def duplex_dense_legs(L, a, dev, lens, rows, per, nf, stride, ends, rehearsal):
+    """The all-full and the mixed-fill leg: the duplex scan against its dense form on the same rows."""
+    med = statistics.median
+    legs = {}
+    m, slots, ab = nf + 1, 1, 64
+    ackLen = 5 + len(ACK_MSG)
+    rng = random.Random(11)
+    fills = [rng.randrange(1, nf + 1) for _ in range(rows)]
+    for leg in ("all_full", "mixed_fill"):
+        if leg == "mixed_fill":
+            # (every frame's header has the same width here, so the first row's frame ends hold for all rows)
+            words = []
+            for k, f in enumerate(fills):
+                if k % ACK_EVERY == 0:
+                    fr = bytes([ackLen - 1, 2]) + (k // per).to_bytes(3, "little") + ACK_MSG
+                    assert L.sgpu_h2d(dev + k * stride + ends[f - 1], fr, len(fr)) == 0
+                    words.append(ends[f - 1] + ackLen)
+                else:
+                    words.append(ends[f - 1])
+            lraw = b"".join(w.to_bytes(4, "little") for w in words)
+            acks = (rows + ACK_EVERY - 1) // ACK_EVERY
+            total = sum(fills) + acks
+            maxRecords = min(rows * m, (total + 1023) & ~1023)
+            maxAcks = min(rows * slots, (acks + 1023) & ~1023)
+        else:
+            lraw = (ends[nf - 1] + ackLen).to_bytes(4, "little") * rows
+            acks = rows
+            total = maxRecords = rows * m
+            maxAcks = rows * slots
+        assert L.sgpu_h2d(lens, lraw, len(lraw)) == 0
+        pBytes = L.sgpu_frames_duplex_bytes(rows, m, slots, ab)
+        dBytes = L.sgpu_frames_duplex_dense_bytes(rows, maxRecords, maxAcks, ab)
+        pOut, dOut = L.sgpu_host_alloc(pBytes), L.sgpu_host_alloc(dBytes)
+        assert pBytes and dBytes and pOut and dOut
+
+        def timed(call):
+            L.sgpu_timing(1, 1, None, None)
+            t0 = time.perf_counter()
+            t = call()
+            assert t > 0 and L.sgpu_gather_wait(t) == 0
+            wall = (time.perf_counter() - t0) * 1e3
+            ms = (C.c_double * 19)()
+            L.sgpu_timing_kernels(ms, 19)
+            return wall, list(ms)
+
+        pw, pk, dw, dk = [], [], [], []
+        for r in range(a.warmup + a.reps):
+            w1, m1 = timed(lambda: L.sgpu_frames_scan_duplex(dev, stride, lens, rows, m, slots, ab, pOut))
+            w2, m2 = timed(lambda: L.sgpu_frames_scan_duplex_dense(dev, stride, lens, rows, m, slots, ab, maxRecords,
+                                                                   maxAcks, dOut))
+            if r >= a.warmup:
+                pw.append(w1)
+                pk.append(m1[12])
+                dw.append(w2)
+                dk.append((m2[12], m2[17], m2[16], m2[18]))
+        info = (C.c_uint * 4).from_address(dOut)
+        assert list(info) == [total, total, rows, acks], "info %r, expected T = W = %d, WA = %d" % (list(info), total, acks)
+        pwords = (C.c_uint * rows).from_address(pOut + rows * m * 32)   # (behind the 32-byte records)
+        assert sum(pwords) == total
+        # the first and the last ack's slot in both outputs
+        first = C.string_at(dOut + L.sgpu_frames_duplex_dense_slots(rows, maxRecords), ab)
+        last = C.string_at(dOut + L.sgpu_frames_duplex_dense_slots(rows, maxRecords) + (acks - 1) * ab, ab)
+        assert first == last == ACK_MSG + bytes(ab - len(ACK_MSG))
+        assert C.string_at(pOut + L.sgpu_frames_duplex_slots(rows, m), ab) == first
+        res = {"frames": total, "acks": acks, "mean_frames_per_row": round(total / rows, 4), "max_frames": m,
+               "ack_slots": slots, "ack_bytes": ab, "max_records": maxRecords, "max_acks": maxAcks,
+               "duplex_bytes": pBytes, "dense_bytes": dBytes}
+        if not rehearsal:
+            res.update({"duplex_wait_ms_median": round(med(pw), 4), "duplex_wait_ms_range": [round(min(pw), 4), round(max(pw), 4)],
+                        "dense_wait_ms_median": round(med(dw), 4), "dense_wait_ms_range": [round(min(dw), 4), round(max(dw), 4)],
+                        "duplex_k_ackwalk_ms_median": round(med(pk), 4),
+                        "dense_k_ackwalkd_ms_median": round(med([k[0] for k in dk]), 4),
+                        "k_rowsum2_ms_median": round(med([k[1] for k in dk]), 4),
+                        "k_compact_ms_median": round(med([k[2] for k in dk]), 4),
+                        "k_slots_ms_median": round(med([k[3] for k in dk]), 4),
+                        "duplex_wait_ms": [round(v, 4) for v in pw], "dense_wait_ms": [round(v, 4) for v in dw],
+                        "dense_over_duplex": round(med(dw) / med(pw), 3)})
+        legs[leg] = res
+        L.sgpu_host_free(pOut)
+        L.sgpu_host_free(dOut)
+    return legs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--library", default=os.path.join(ROOT, "siamese_amd", "libsiamese_amd.so"))
@@ -136,12 +240,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--dense", action="store_true", help="add the all-full and mixed-fill legs of the dense scan")
+    ap.add_argument("--duplex-dense", action="store_true",
+                    help="add the all-full and mixed-fill legs of the dense duplex scan (run last: they rewrite rows)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     rehearsal = "hostsim" in os.path.basename(a.library)
 
-    from siamese_amd.binding import ROW_OK, PackedHead, RowHead, bind_dense_abi
+    from siamese_amd.binding import ROW_OK, PackedHead, RowHead, bind_dense_abi, bind_duplex_dense_abi
     L = bind_dense_abi(C.CDLL(a.library))
+    if a.duplex_dense:
+        bind_duplex_dense_abi(L)
     L.sgpu_device_alloc.restype = C.c_void_p
     L.sgpu_device_alloc.argtypes = [C.c_size_t]
     L.sgpu_host_alloc.restype = C.c_void_p
@@ -185,6 +293,9 @@ def main():
                     ends.append(len(row))
             assert len(row) <= stride
             lw.append(len(row).to_bytes(4, "little"))
+            if a.duplex_dense:   # (behind the row's length: only the duplex legs, which set their own lengths, see it)
+                row += bytes([4 + len(ACK_MSG), 2]) + i.to_bytes(3, "little") + ACK_MSG
+                assert len(row) <= stride
             block.append(bytes(row) + bytes(stride - len(row)))
         blob, lraw = b"".join(block), b"".join(lw)
         assert L.sgpu_h2d(dev + i * per * stride, blob, len(blob)) == 0
@@ -237,6 +348,8 @@ def main():
             kn.append(k)
             cp.append(c)
     dense = dense_legs(L, a, dev, lens, rows, nf, stride, ends, rehearsal) if a.dense else None
+    duplexDense = (duplex_dense_legs(L, a, dev, lens, rows, per, nf, stride, ends, rehearsal)
+                   if a.duplex_dense else None)
     L.sgpu_timing(0, 1, None, None)
 
     # spot check: first and last flow, first and last row, every frame
@@ -269,6 +382,8 @@ def main():
         out["rehearsal"] = "CPU test double: call sequence only, no time"
     if dense:
         out["dense"] = dense
+    if duplexDense:
+        out["duplex_dense"] = duplexDense
     line = json.dumps(out)
     print(line)
     if a.out:
