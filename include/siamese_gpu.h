@@ -1155,7 +1155,12 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// the elimination's outcome is known -- a singular device job counts here
 /// once, and the host's repeat of its elimination, which pivots again, once
 /// more -- and [38] the device jobs, chained or not, that came back singular,
-/// then [39] the rows scanned by sgpu_frames_scan_duplex_dense, counted as [36];
+/// then [39] the rows scanned by sgpu_frames_scan_duplex_dense, counted as [36],
+/// then, counted when a solve's submission has completed, [40] the solves
+/// whose product (X = T R) had non-zero bytes past a recovered length, so that
+/// the exact sweeps redid them (inconsistent recovery data; always 0 where no
+/// product solve runs), and [41] the solves that stopped at an invalid
+/// recovered length prefix (the decoder is disabled, as the reference's);
 /// count entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'

@@ -2405,6 +2405,11 @@ __device__ void solve_prefix_wave(uint32_t m, uint32_t lane, uint32_t (&p4)[4], 
         __builtin_amdgcn_wave_barrier();
         for (uint32_t k = lane; k <= m; k += 64)
             out[k] = rw[k];
+        // the product solves' tail flag: clear on every path (k_solve_tr, which
+        // runs after this pass where it runs at all, sets it), so that the host
+        // reads it of every completed solve (sgpu_engine_stats_ex [40])
+        if (lane == 0)
+            out[m + 1] = 0;
         // one atomic per wave (per-lane global atomics serialise at one address)
 #pragma unroll
         for (unsigned d = 32; d >= 1; d >>= 1) {

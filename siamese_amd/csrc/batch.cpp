@@ -1420,7 +1420,7 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
     const Engine* e = Engine::global();
-    const uint64_t v[40] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[42] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
@@ -1432,8 +1432,8 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
                             e->rows_shape(0), e->rows_shape(1), e->rows_shape(2), e->rows_shape(3),
                             e->rows_shape(4), be_exec_stage_cap(),
                             e->denses(),  s.gePivoted,   s.geSingular,
-                            e->duplex_denses()};
-    for (unsigned k = 0; k < count && k < 40; ++k)
+                            e->duplex_denses(), e->solves_flagged(), e->solves_cut()};
+    for (unsigned k = 0; k < count && k < 42; ++k)
         out[k] = v[k];
 }
 

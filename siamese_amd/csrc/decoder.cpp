@@ -2818,6 +2818,10 @@ SiameseResult DecoderCore::publish_final(unsigned slot)
         std::lock_guard<std::mutex> g(res_->mu);
         const PendingDecode& pd = res_->pend[slot];
         ready = pd.done && pd.words.size() > m && pd.words[0] == m;
+        // (held until here, so complete_solve left the counting to this call;
+        // not done yet: solve_publish releases it and complete_solve counts)
+        if (pd.done && pd.held)
+            count_outcome(pd);
     }
     if (!ready) {
         const SiameseResult res = solve_publish(slot);
@@ -2895,11 +2899,23 @@ void DecoderCore::fill_entry(const PendingDecode& pd, unsigned ci, SiameseOrigin
 }
 
 // Engine completer thread: the submission carrying the solve has completed.
+// sgpu_engine_stats_ex [40] and [41]: a completed solve that the product path
+// handed back to the sweeps, one that stopped at an invalid length prefix.
+void DecoderCore::count_outcome(const PendingDecode& pd)
+{
+    Engine::global()->count_solve_outcome(pd.words[pd.m + 1] != 0, pd.words[0] < pd.m);
+}
+
 void DecoderCore::complete_solve(Resolver& r, unsigned slot, const uint32_t* results)
 {
     std::lock_guard<std::mutex> g(r.mu);
     PendingDecode& pd = r.pend[slot];
-    pd.words.assign(results + pd.base, results + pd.base + pd.m + 1);
+    // words 0..m and the product solves' tail flag, word m + 1
+    pd.words.assign(results + pd.base, results + pd.base + pd.m + 2);
+    // (a chained solve's words mean something only if its job succeeded:
+    // publish_final counts it)
+    if (pd.live && !pd.held)
+        count_outcome(pd);
     for (const auto& t : pd.targets)
         fill_entry(pd, t.first, *t.second);
     pd.targets.clear();

@@ -569,7 +569,8 @@ private:
         bool live = false;            // queued, not yet applied to the decoder's slots
         bool done = false;            // the completion arrived: `words` holds the results
         bool held = false;            // a chained solve not yet published (apply_resolved skips it)
-        std::vector<uint32_t> words;  // [0] rows recovered, [1 + ci] header << 29 | length
+        // [0] rows recovered, [1 + ci] header << 29 | length, [m + 1] the product solve's tail flag
+        std::vector<uint32_t> words;
         /// caller-owned outputs to fill at completion (deferred API): (ci, entry)
         std::vector<std::pair<unsigned, SiameseOriginalPacket*>> targets;
     };
@@ -595,6 +596,7 @@ private:
         bool geDone = false;
     };
     static void complete_solve(Resolver& r, unsigned slot, const uint32_t* results);
+    static void count_outcome(const PendingDecode& pd);
     static void fill_entry(const PendingDecode& pd, unsigned ci, SiameseOriginalPacket& out);
     void apply_resolved();
     void publish_outputs();   // Resolver::out* = recovered_ (caller holds res_->mu)

@@ -1012,6 +1012,11 @@ private:
     // rows scanned by the duplex dense scan, counted as walks_ ([39]); behind every other member, so that
     // none of them moves
     std::atomic<uint64_t> duplexDenses_{0};
+    // completed solves whose product came back flagged (result word m + 1 non-zero: bytes past a recovered
+    // length, redone by the sweeps) and those that stopped at an invalid length prefix (word 0 below m),
+    // counted by the completion (DecoderCore::complete_solve; [40], [41]); here for the same reason
+    std::atomic<uint64_t> solvesFlagged_{0};
+    std::atomic<uint64_t> solvesCut_{0};
 
 public:
     uint64_t rows_shape(unsigned k) const { return rowsShape_[k].load(std::memory_order_relaxed); }
@@ -1020,6 +1025,15 @@ public:
     uint64_t concats() const { return concats_.load(std::memory_order_relaxed); }
     uint64_t denses() const { return denses_.load(std::memory_order_relaxed); }
     uint64_t duplex_denses() const { return duplexDenses_.load(std::memory_order_relaxed); }
+    uint64_t solves_flagged() const { return solvesFlagged_.load(std::memory_order_relaxed); }
+    uint64_t solves_cut() const { return solvesCut_.load(std::memory_order_relaxed); }
+    void count_solve_outcome(bool flagged, bool cut)
+    {
+        if (flagged)
+            solvesFlagged_.fetch_add(1, std::memory_order_relaxed);
+        if (cut)
+            solvesCut_.fetch_add(1, std::memory_order_relaxed);
+    }
     uint64_t duplexes() const { return duplexes_.load(std::memory_order_relaxed); }
     uint64_t ack_frames() const { return ackFrames_.load(std::memory_order_relaxed); }
     void count_ack_frames(uint64_t n) { ackFrames_.fetch_add(n, std::memory_order_relaxed); }

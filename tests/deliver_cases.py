@@ -140,10 +140,18 @@ class Stream:
     all).  ranges: the encoder takes the originals by one
     sgpu_encoder_add_range call and the decoder each unbroken stretch of
     received ones by one sgpu_decoder_add_original_range call, both with a
-    bytes[] array."""
+    bytes[] array.  given: {index: bytes} the decoder is handed for those
+    received originals in place of the encoder's (solve_cases.py: a damaged
+    or shortened packet), from a buffer of their own, by a per-packet
+    sgpu_decoder_add_original (a range call's ingest rides on the encoder's
+    descriptor and would take the encoder's bytes)."""
 
-    def __init__(self, L, lengths, lost=(), recovery=0, seed=1, pitch=None, data=None, offsets=None, ranges=False):
+    def __init__(self, L, lengths, lost=(), recovery=0, seed=1, pitch=None, data=None, offsets=None, ranges=False,
+                 given=None):
         self.L = L
+        self.given = dict(given or {})
+        assert not (ranges and self.given), "an altered original goes in by a per-packet call"
+        assert all(i not in lost and 0 < len(g) <= lengths[i] for i, g in self.given.items())
         self.data = data or [payload(seed * 1000 + i, n) for i, n in enumerate(lengths)]
         assert [len(d) for d in self.data] == list(lengths)
         count = len(lengths)
@@ -159,6 +167,16 @@ class Stream:
             blob[o:o + len(d)] = d
         self.src = L.sgpu_device_alloc(len(blob))
         assert self.src and L.sgpu_h2d(self.src, bytes(blob), len(blob)) == 0
+        # the decoder's own copies, at odd addresses like the encoder's
+        self.alt = None
+        if self.given:
+            self.altAt = {}
+            ablob = bytearray(3 + self.pitch * len(self.given))
+            for k, (i, g) in enumerate(sorted(self.given.items())):
+                self.altAt[i] = 3 + k * self.pitch
+                ablob[self.altAt[i]:self.altAt[i] + len(g)] = g
+            self.alt = L.sgpu_device_alloc(len(ablob))
+            assert self.alt and L.sgpu_h2d(self.alt, bytes(ablob), len(ablob)) == 0
         lens = (C.c_uint * count)(*lengths)
         self.enc = None
         self.recs = None
@@ -196,7 +214,10 @@ class Stream:
                 i = j + 1
         else:
             for i, d in enumerate(self.data):
-                if i not in lost:
+                if i in self.given:
+                    assert L.sgpu_decoder_add_original(self.dec, i, self.alt + self.altAt[i],
+                                                       len(self.given[i])) == SUCCESS
+                elif i not in lost:
                     assert L.sgpu_decoder_add_original(self.dec, i, self.at(i), len(d)) == SUCCESS
         for k in range(recovery):
             assert L.sgpu_decoder_add_recovery(self.dec, C.byref(self.recs[k])) == SUCCESS
@@ -216,6 +237,8 @@ class Stream:
         self.L.sgpu_decoder_free(self.dec)
         assert self.L.sgpu_flush() == 0   # (nothing queued still reads the sources)
         self.L.sgpu_device_free(self.src)
+        if self.alt:
+            self.L.sgpu_device_free(self.alt)
 
 
 def stats(L):

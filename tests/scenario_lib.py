@@ -166,8 +166,8 @@ ENGINE_KEYS = ("flushes launches ops terms solves ingests upload_bytes ref_op_by
                "delivers frames scans walks relays packs duplexes ack_frames concats "
                "rows_batches rows_versioned rows_versioned_rows rows_unfit rows_unstaged "
                "stage_cap "
-               # [36..38]
-               "denses ge_pivoted ge_singular").split()
+               # [36..41]
+               "denses ge_pivoted ge_singular duplex_denses solves_flagged solves_cut").split()
 
 
 def engine_dict(report):

@@ -594,6 +594,12 @@ static void solve_prefix(const SolveDesc* solves, const SolveRow* rows, const ui
         const SolveRow* R = rows + sd.rowBegin;
         const uint8_t* C = coef + sd.coefOffset;
         uint32_t* out = results + sd.result;
+        // Word m + 1 is the product solves' tail flag (k_solve_tr sets it when
+        // a product row has non-zero bytes past its recovered length, and
+        // k_solve_main then redoes that solve by the sweeps).  There is no
+        // product path here, only the sweeps: always 0, so the host counts no
+        // flagged solve on the double (sgpu_engine_stats_ex [40]).
+        out[m + 1] = 0;
         if (noexec()) {
             out[0] = m;
             for (uint32_t i = 0; i < m; ++i)

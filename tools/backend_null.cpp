@@ -101,6 +101,7 @@ static void solve_prefix(const SolveDesc* solves, const SolveRow*, const uint8_t
         out[0] = sd[s].m;
         for (uint32_t i = 0; i < sd[s].m; ++i)
             out[1 + i] = (2u << 29) | g_len;
+        out[1 + sd[s].m] = 0;   // the product solves' tail flag: never set here
     }
 }
 
