@@ -714,6 +714,99 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders,
                                                     const void* deviceRows, size_t stride, unsigned count,
                                                     SiameseResult* results /* maxRecords, optional */,
                                                     unsigned* rowsOut, unsigned* acceptedOut);
+/*
+    Rows that are byte streams.  The scans above take a row as one datagram: a
+    frame that does not end inside it is malformed.  A per-connection receive
+    buffer in device memory (a stream transport, an RDMA ring, a relay's
+    sgpu_frames_send-style stream landing on another GPU) holds frames back to
+    back instead, and its last frame is usually still arriving.  The stream scan
+    walks row bytes [start, end), tells a frame that the data does not yet hold
+    whole (partial) from one that is wrong (malformed), and says for every row
+    where its next scan starts:
+
+        bytes  = sgpu_frames_streams_bytes(count, maxRecords);    // pinned, sgpu_host_alloc
+        for (;;) {
+            // the transport has advanced ends[k]; starts[k] is where row k's last scan stopped
+            ticket = sgpu_frames_scan_streams(rows, stride, starts, ends, count, maxFrames, maxRecords, out);
+            sgpu_gather_wait(ticket);
+            sgpu_frames_recv_streams(decoders, n, out, maxFrames, maxRecords, rows, stride, count,
+                                     results, consumed, &rowsDone, &accepted);
+            // consumed[k], k < rowsDone, is row k's next start: write it back to starts[k]
+            // (rows from rowsDone on keep their old starts and are scanned again);
+            // when a start nears stride, move the row's bytes [start, end) to its front
+        }
+
+    out holds sgpu_frames_scan_dense's layout, sgpu_frames_dense_bytes(count,
+    maxRecords) bytes of it, and then, at sgpu_frames_streams_next(count,
+    maxRecords), count uint32 next words and zeros up to the next 16-byte
+    boundary.  Every byte is written by every scan.  A record's Offset is
+    relative to the row's first byte, not to start.  Still not offered: a ring
+    that wraps around inside a row (compact it, or map it twice), ack frames in
+    stream rows (the duplex scans take those), and more than 256 frames per row
+    and scan (resume from the next word).
+*/
+#define SGPU_STREAM_PARTIAL 0x20000000u  /* row word: the walk stopped at a frame the data does not yet hold whole */
+
+/// Bytes of a stream scan's output (0 where sgpu_frames_dense_bytes is 0).
+SIAMESE_EXPORT size_t sgpu_frames_streams_bytes(unsigned count, unsigned maxRecords);
+/// Byte offset of the next words in a stream scan's output: sgpu_frames_dense_bytes(count, maxRecords).
+SIAMESE_EXPORT size_t sgpu_frames_streams_next(unsigned count, unsigned maxRecords);
+/// Scan `count` byte-stream rows into pinnedOut (pinned, 16-byte aligned,
+/// sgpu_frames_streams_bytes): a gather with sgpu_frames_scan_dense's ticket,
+/// ordering and lifetime contract, its rows, stride, maxFrames and maxRecords.
+///
+/// Row k is walked over its bytes [start, end), start = deviceStarts ?
+/// deviceStarts[k] : 0 and end = deviceEnds ? deviceEnds[k] : stride (uint32
+/// arrays in device memory, 4-byte aligned; byte offsets from the row's first
+/// byte, at any alignment), as sgpu_frames_scan_packed walks a row from 0: zero
+/// bytes where a frame would start are skipped, the prefix is judged with the
+/// bytes left before end, and a frame is accepted under sgpu_frames_scan_rows'
+/// per-frame rules (types 0 and 1).  Row word k and next word k say how the walk
+/// ended:
+///   - start > end or end > stride: SGPU_PACKED_MALFORMED, no records, next =
+///     min(start, stride);
+///   - only zero bytes were left: the count n, next = end;
+///   - n == maxFrames and a non-zero byte is left: n | SGPU_PACKED_MORE, next =
+///     that byte's offset;
+///   - a partial frame at `at`: n | SGPU_STREAM_PARTIAL, next = at.  With left =
+///     end - at, the frame is partial when its first byte announces a prefix of
+///     w bytes and left < w, or the prefix gives L >= 1 and w + L > left, and
+///     nothing that is present is wrong already;
+///   - a frame at `at` that is whole and fails a rule (L == 0 included), or that
+///     is cut off and can never become valid -- w + L > stride, a type byte that
+///     is present and above 1, a type byte that is present with L not above the
+///     type's inner header, an original whose three PacketNum bytes are present
+///     and exceed SIAMESE_PACKET_NUM_MAX -- : n | SGPU_PACKED_MALFORMED, next =
+///     at, so that a connection never stalls on junk.
+/// (With a null deviceEnds and a stride of 4 GiB, next = end is stated as 2^32 -
+/// 1.)  With start 0 and no partial frame the first sgpu_frames_dense_bytes bytes
+/// are sgpu_frames_scan_dense's on the same rows and sizes, byte for byte.
+/// Nothing outside [row, row + stride) and the row's two words is read.
+///
+/// Returns -1, with nothing queued, where sgpu_frames_scan_dense does, for a
+/// misaligned deviceStarts or deviceEnds and for an output of 4 GiB or more.
+/// count == 0 returns a valid ticket that is already complete.
+SIAMESE_EXPORT long long sgpu_frames_scan_streams(const void* deviceRows, size_t stride,
+                                                  const unsigned* deviceStarts, const unsigned* deviceEnds,
+                                                  unsigned count, unsigned maxFrames, unsigned maxRecords,
+                                                  void* pinnedOut);
+/// Host only: sgpu_frames_recv_dense for a stream scan's output, with the same
+/// routing, results, *rowsOut and *acceptedOut and the same checks of info,
+/// words, starts and records.  A word may carry SGPU_STREAM_PARTIAL, which is no
+/// error and adds nothing to the return value; SGPU_PACKED_MALFORMED contributes
+/// Siamese_InvalidInput after the row's good frames, as there.  For a row k < c,
+/// next[k] <= stride and, when the row has records, next[k] >= the end of its
+/// last record are checked before the row's records are touched: a next word
+/// that fails stops the routing as a start that fails does.  consumedOut[k] =
+/// next[k] for k < *rowsOut; the entries from *rowsOut on are left untouched
+/// (scan those rows again from their old starts).  Arguments are refused as in
+/// sgpu_frames_recv_dense, and a null consumedOut with count > 0.
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_streams(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                      const void* heads, unsigned maxFrames, unsigned maxRecords,
+                                                      const void* deviceRows, size_t stride, unsigned count,
+                                                      SiameseResult* results /* maxRecords, optional */,
+                                                      unsigned* consumedOut /* count, host */,
+                                                      unsigned* rowsOut, unsigned* acceptedOut);
 /// Queue a stream's frames packed into MTU-sized rows: the present originals
 /// firstPacketNum .. firstPacketNum+originalCount-1 of `encoder`, ascending, as
 /// SGPU_FRAME_ORIGINAL, then `recovery` (this encoder's current output) as
@@ -1112,7 +1205,9 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// (sgpu_frames_scan_dense, counted as k_walk is; the dense scan's walk is
 /// counted under [8]), [17] k_rowsum2 and [18] k_slots
 /// (sgpu_frames_scan_duplex_dense, likewise; its walk is counted under [12] and
-/// its record copy under [16]); count entries at most.
+/// its record copy under [16]), [19] k_streamwalk (sgpu_frames_scan_streams,
+/// likewise; its k_rowsum and k_compact are counted under [15] and [16]); count
+/// entries at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -1160,8 +1255,9 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// whose product (X = T R) had non-zero bytes past a recovered length, so that
 /// the exact sweeps redid them (inconsistent recovery data; always 0 where no
 /// product solve runs), and [41] the solves that stopped at an invalid
-/// recovered length prefix (the decoder is disabled, as the reference's);
-/// count entries at most.
+/// recovered length prefix (the decoder is disabled, as the reference's), then
+/// [42] the rows scanned by sgpu_frames_scan_streams, counted as [36]; count
+/// entries at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

@@ -87,6 +87,25 @@ def bind_dense_abi(L):
     return L
 
 
+STREAM_PARTIAL = 0x20000000
+
+
+def bind_streams_abi(L):
+    """Prototypes of the scan of byte-stream rows (sgpu_frames_scan_streams and
+    sgpu_frames_recv_streams) and of bind_dense_abi's calls."""
+    vp, u, sz = ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t
+    bind_dense_abi(L)
+    L.sgpu_frames_streams_bytes.restype = sz
+    L.sgpu_frames_streams_bytes.argtypes = [u, u]
+    L.sgpu_frames_streams_next.restype = sz
+    L.sgpu_frames_streams_next.argtypes = [u, u]
+    L.sgpu_frames_scan_streams.restype = ctypes.c_longlong
+    L.sgpu_frames_scan_streams.argtypes = [vp, sz, vp, vp, u, u, u, vp]
+    L.sgpu_frames_recv_streams.restype = ctypes.c_int
+    L.sgpu_frames_recv_streams.argtypes = [vp, u, vp, u, u, vp, sz, u, vp, vp, vp, vp]
+    return L
+
+
 def bind_relay_pack_abi(L):
     """Prototype of sgpu_decoder_pack_frames: a decoder's packets as wire
     frames packed several to a row, laid out on the device."""

@@ -252,6 +252,19 @@ bool be_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint
 bool be_duplex_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint32_t count,
                           uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes, uint32_t maxRecords,
                           uint32_t maxAcks, void* devStage, void* hostOut, void** packed, void** landed);
+/// The scan of byte-stream rows (ops.h streams_bytes): three launches on the
+/// gather stream -- k_streamwalk's walk of row bytes [starts[k], ends[k]) with
+/// the row's records into the scratch area at streams_scratch_offset(count,
+/// maxRecords), the row words into the output and the next words behind its
+/// dense part, then k_rowsum and k_compact as in be_dense_rows -- all into
+/// devStage (streams_stage_bytes(count, maxFrames, maxRecords), device memory,
+/// 16-byte aligned), then one copy of the first streams_bytes(count, maxRecords)
+/// bytes to hostOut (pinned), without waiting.  starts and ends: the rows' two
+/// words in device memory, each or both null (0 and stride).  rows, stride and
+/// the marks are be_scan_rows'.
+bool be_stream_rows(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends, uint32_t count,
+                    uint32_t maxFrames, uint32_t maxRecords, void* devStage, void* hostOut, void** packed,
+                    void** landed);
 /// Block until the device has passed `mark`, then recycle it; false on a
 /// device fault.
 bool be_mark_sync(void* mark);
@@ -259,10 +272,11 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-/// (kBeScan, kBeWalk, kBeAckWalk, kBeRowsum, kBeCompact, kBeRowsum2 and kBeSlots are bracketed on
+/// (kBeScan, kBeWalk, kBeAckWalk, kBeRowsum, kBeCompact, kBeRowsum2, kBeSlots and kBeStreamWalk are bracketed on
 /// the gather stream: be_sync waits for a bracket of those classes still in flight before it folds
 /// it in; the dense scan's walk is counted as kBeWalk, the duplex dense scan's as kBeAckWalk and
-/// its k_compact as kBeCompact)
+/// its k_compact as kBeCompact; the stream scan's walk has its own class, its k_rowsum and k_compact are
+/// counted as kBeRowsum and kBeCompact)
 enum BeKernel
 {
     kBeIngest,
@@ -284,6 +298,7 @@ enum BeKernel
     kBeCompact,
     kBeRowsum2,
     kBeSlots,
+    kBeStreamWalk,
     kBeKernelKinds
 };
 void be_timing_enable(bool on);

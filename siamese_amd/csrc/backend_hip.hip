@@ -4874,6 +4874,321 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(uint64_t out, uint6
 }
 
 // ---------------------------------------------------------------------------
+// Stream row walk (k_streamwalk, ops.h kStreamPartial; frames.h stream_walk is
+// the statement)
+//
+// The dense scan for rows that are byte streams: row bytes [start, end) hold
+// frames back to back and the last one may be cut off by end.  walk_row's lane
+// per row is bound by a chain of dependent loads, one frame at a time; here a
+// wave takes the row, kStreamChunk bytes at a time, and the chain is followed
+// in LDS.  A chunk starts at the 16-byte word that holds the cursor: lane l
+// loads word l, lane 0 also the word behind the chunk (a header of up to 11
+// bytes that starts in the chunk's last bytes ends there), words at or past the
+// stride read as zero.  Every lane then judges, for its 16 byte positions, the
+// frame that would start there (stream_hop: walk_row's rules plus the partial
+// rule) and leaves the hop in LDS: the next position after a zero byte, the
+// position behind an accepted frame, or kStreamChunk for every hop that leaves
+// the chunk or stops the walk.  The positions the walk really visits are the
+// chain from the cursor; it is found by pointer doubling: in round r every
+// reached position marks the one 2^r hops behind it and hands it its rank (the
+// frames before it), then every position squares its hop.  A round that marks
+// nothing ends the search, so a chunk of a few long frames takes two or three
+// rounds and only a chunk of zero bytes takes all ten.  The lanes that own
+// reached frames then build their records from the staged bytes and store them
+// at slot n + rank of the row's scratch slots; a recovery frame's tail is one
+// or two global loads per lane, independent of every other lane's, so the tail
+// loads of a chunk's frames are in flight together.  The wave carries the
+// cursor, the count and the flags into the next chunk, which starts where the
+// last hop landed: the chunks inside a long frame are never loaded.  A wave's
+// LDS accesses are executed in order, so what one lane wrote is there for
+// another lane's later read; wave_lds_sync only keeps the compiler from moving
+// accesses across the hand-over.  No workgroup barrier (the waves of a
+// workgroup share nothing), no atomics.  k_rowsum masks the row word with
+// kPackedCountMask before it sums, so kStreamPartial rides along in the word as
+// kPackedMore and kPackedMalformed do, and k_compact reads only the starts: both
+// run unchanged behind this walk.
+
+constexpr uint32_t kStreamWaves = kStreamWalkThreads / 64;
+constexpr uint32_t kStreamPer = kStreamChunk / 64;   // byte positions per lane
+constexpr uint32_t kStreamNone = 0xffffu;            // rank of a position the chain has not reached
+static_assert(kStreamChunk == 64 * 16 && kStreamChunk < kStreamNone, "a chunk is one 16-byte word per lane");
+
+// what the walk does at a byte position
+enum : uint32_t
+{
+    kHopZero,      // a zero byte: on to the next position
+    kHopFrame,     // an accepted frame: on to the position behind it
+    kHopExit,      // (of a chunk's last position only: the hop leaves the chunk)
+    kHopEnd,       // the row's bytes are used up
+    kHopPartial,   // a frame the data does not yet hold whole
+    kHopBad        // a frame that is malformed, or cut off and never valid
+};
+struct StreamHop
+{
+    uint32_t kind, h, L;
+    uint64_t x;   // row bytes [a + h, a + h + 8): type, flow, then PacketNum or the packet's first bytes
+};
+
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The frame that would start at row offset a < end, from row bytes [a, a + 12)
+// (y0..y2; only those before end are used).
+__device__ __forceinline__ StreamHop stream_hop(uint32_t y0, uint32_t y1, uint32_t y2, uint64_t a, uint64_t end,
+                                                uint64_t stride)
+{
+    StreamHop r = {kHopZero, 0, 0, 0};
+    if ((y0 & 0xffu) == 0)
+        return r;
+    const uint64_t left = end - a;
+    uint32_t L = 0;
+    const int hp = parse_prefix(y0, left < 4 ? (uint32_t)left : 4u, &L);
+    if (hp < 1) {   // the prefix itself is cut off
+        r.kind = kHopPartial;
+        return r;
+    }
+    if (L < 1) {
+        r.kind = kHopBad;
+        return r;
+    }
+    const uint32_t h = (uint32_t)hp;
+    const uint64_t x = (pack64(y0, y1) >> (8u * h)) | ((uint64_t)y2 << (64u - 8u * h));
+    const uint32_t type = (uint32_t)x & 0xffu;
+    const uint32_t inner = type == 0 ? 7u : 4u;
+    const uint32_t num = type == 0 ? (uint32_t)(x >> 32) & 0xffffffu : 0u;
+    r.h = h;
+    r.L = L;
+    r.x = x;
+    if ((uint64_t)h + L <= left) {
+        r.kind = type <= 1 && L > inner && num <= 0x3fffffu ? kHopFrame : kHopBad;
+        return r;
+    }
+    const uint64_t have = left - h;   // bytes of the frame's body that are there
+    bool never = (uint64_t)h + L > stride;
+    if (have >= 1)
+        never = never || type > 1 || L <= inner;
+    if (have >= 7)
+        never = never || num > 0x3fffffu;
+    r.kind = never ? kHopBad : kHopPartial;
+    return r;
+}
+
+__global__ __launch_bounds__(kStreamWalkThreads) void k_streamwalk(uint64_t rows, uint64_t stride,
+                                                                   const uint32_t* __restrict__ starts,
+                                                                   const uint32_t* __restrict__ ends, uint32_t count,
+                                                                   uint32_t maxFrames, uint64_t scratch,
+                                                                   uint64_t words, uint64_t nexts)
+{
+    constexpr uint32_t C = kStreamChunk;
+    __shared__ uint4 sBytes[kStreamWaves][C / 16 + 1];
+    __shared__ uint16_t sJmp[kStreamWaves][C], sCnt[kStreamWaves][C], sRank[kStreamWaves][C];
+    __shared__ uint32_t sLast[kStreamWaves][4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t k = (uint64_t)blockIdx.x * kStreamWaves + wave;
+    if (k >= count)   // (wave-uniform)
+        return;
+    const uint32_t* B = reinterpret_cast<const uint32_t*>(sBytes[wave]);
+    uint16_t* jmp = sJmp[wave];
+    uint16_t* cnt = sCnt[wave];
+    uint16_t* rank = sRank[wave];
+    uint32_t* last = sLast[wave];
+    const uint64_t row = rows + k * stride;
+    const uint64_t start = starts ? starts[k] : 0, end = ends ? ends[k] : stride;
+    const uint64_t rec = scratch + k * maxFrames * 32;
+    // row bytes [base + p, base + p + 12) of the staged chunk
+    auto bytes12 = [&](uint32_t p, uint32_t& y0, uint32_t& y1, uint32_t& y2) {
+        const uint32_t q = p >> 2, s = p & 3u;
+        const uint32_t x0 = B[q], x1 = B[q + 1], x2 = B[q + 2], x3 = B[q + 3];
+        y0 = __builtin_amdgcn_alignbyte(x1, x0, s);
+        y1 = __builtin_amdgcn_alignbyte(x2, x1, s);
+        y2 = __builtin_amdgcn_alignbyte(x3, x2, s);
+    };
+    uint32_t n = 0, flags = 0;
+    uint64_t at = start, next = end;
+    bool open = true;
+    if (start > end || end > stride) {
+        flags = kPackedMalformed;
+        next = start < stride ? start : stride;
+        open = false;
+    }
+    while (open && at < end) {   // (all wave-uniform)
+        const uint64_t base = at & ~(uint64_t)15;
+        const uint32_t entry = (uint32_t)(at - base);
+        // 1. stage the chunk and its halo
+        {
+            const uint64_t a = base + lane * 16;
+            sBytes[wave][lane] = a < stride ? ld16(row + a) : make_uint4(0, 0, 0, 0);
+            if (lane == 0) {
+                sBytes[wave][C / 16] = base + C < stride ? ld16(row + base + C) : make_uint4(0, 0, 0, 0);
+                // (step 4 overwrites this with the chain's last position: a chunk can only end the walk or
+                // move the cursor on, whatever the chain turns out to be)
+                last[0] = kHopBad;
+                last[1] = 0;
+                last[2] = (uint32_t)at;
+                last[3] = (uint32_t)(at >> 32);
+            }
+        }
+        wave_lds_sync();
+        // 2. every position's hop
+#pragma unroll
+        for (uint32_t i = 0; i < kStreamPer; ++i) {
+            const uint32_t p = i * 64 + lane;
+            const uint64_t a = base + p;
+            uint32_t j = C, c = 0;
+            if (a < end) {
+                uint32_t y0, y1, y2;
+                bytes12(p, y0, y1, y2);
+                const StreamHop hop = stream_hop(y0, y1, y2, a, end, stride);
+                if (hop.kind == kHopZero) {
+                    j = p + 1;
+                } else if (hop.kind == kHopFrame) {
+                    const uint32_t t = p + hop.h + hop.L;   // (L < 2^29)
+                    j = t < C ? t : C;
+                    c = 1;
+                }
+            }
+            jmp[p] = (uint16_t)j;
+            cnt[p] = (uint16_t)c;
+            rank[p] = (uint16_t)(p == entry ? 0u : kStreamNone);
+        }
+        wave_lds_sync();
+        // 3. the chain from the entry, by pointer doubling
+        for (;;) {
+            uint32_t r[kStreamPer], j[kStreamPer], c[kStreamPer], jj[kStreamPer], cc[kStreamPer];
+#pragma unroll
+            for (uint32_t i = 0; i < kStreamPer; ++i) {
+                const uint32_t p = i * 64 + lane;
+                r[i] = rank[p];
+                j[i] = jmp[p];
+                c[i] = cnt[p];
+                jj[i] = j[i] < C ? jmp[j[i]] : C;
+                cc[i] = j[i] < C ? cnt[j[i]] : 0u;
+            }
+            wave_lds_sync();
+            bool marked = false;
+#pragma unroll
+            for (uint32_t i = 0; i < kStreamPer; ++i) {
+                const uint32_t p = i * 64 + lane;
+                if (r[i] != kStreamNone && j[i] < C) {   // (one reached position at most hops to j)
+                    rank[j[i]] = (uint16_t)(r[i] + c[i]);
+                    marked = true;
+                }
+                jmp[p] = (uint16_t)jj[i];
+                cnt[p] = (uint16_t)(c[i] + cc[i]);
+            }
+            wave_lds_sync();
+            if (!__any(marked))
+                break;
+        }
+        // 4. the reached frames' records; the chain's last position says how the chunk ends
+        const uint32_t room = maxFrames - n;
+        uint32_t morePos = C;   // the first reached non-zero byte with `room` frames before it
+#pragma unroll
+        for (uint32_t i = 0; i < kStreamPer; ++i) {
+            const uint32_t p = i * 64 + lane;
+            const uint64_t a = base + p;
+            const uint32_t r = rank[p];
+            if (r == kStreamNone)
+                continue;
+            uint32_t kind = kHopEnd, frames = r;
+            uint64_t pos = a;
+            bool isLast = true;
+            if (a < end) {
+                uint32_t y0, y1, y2;
+                bytes12(p, y0, y1, y2);
+                const StreamHop hop = stream_hop(y0, y1, y2, a, end, stride);
+                kind = hop.kind;
+                if (kind == kHopZero) {
+                    isLast = p + 1 == C;
+                    kind = kHopExit;
+                    pos = a + 1;
+                } else if (r >= room) {
+                    morePos = p < morePos ? p : morePos;
+                    isLast = false;
+                } else if (kind == kHopFrame) {
+                    const uint32_t h = hop.h, L = hop.L, total = h + L;
+                    const uint64_t x = hop.x;
+                    const uint32_t type = (uint32_t)x & 0xffu;
+                    const uint32_t inner = type == 0 ? 7u : 4u;
+                    const uint32_t flow = (uint32_t)(x >> 8) & 0xffffffu;
+                    const uint32_t num = type == 0 ? (uint32_t)(x >> 32) & 0xffffffu : 0u;
+                    const uint32_t D = L - inner;
+                    uint32_t head = 0, T = 0;
+                    uint64_t tail = 0;
+                    if (type == 1) {
+                        head = (uint32_t)(x >> 32) & byte_mask((int)D);
+                        T = D < 8 ? D : 8;
+                        const uint64_t fe = a + total;   // the tail is row bytes [fe - T, fe), fe <= end
+                        const uint64_t s0 = fe - T;
+                        const uint64_t wlo = s0 & ~(uint64_t)15, whi = (fe - 1) & ~(uint64_t)15;   // (whi < stride)
+                        const uint4 ta = ld16(row + wlo);
+                        const uint4 tb = whi != wlo ? ld16(row + whi) : make_uint4(0, 0, 0, 0);
+                        const uint32_t ts = (uint32_t)s0 & 15u;
+                        const uint64_t e0 = pack64(ta.x, ta.y), e1 = pack64(ta.z, ta.w), e2 = pack64(tb.x, tb.y);
+                        const uint64_t TA = (ts & 8u) ? e1 : e0, TB = (ts & 8u) ? e2 : e1;
+                        const uint32_t tsh = 8u * (ts & 7u);
+                        uint64_t v = TA >> tsh;
+                        if (tsh)
+                            v |= TB << (64u - tsh);
+                        if (T < 8)
+                            v &= ((uint64_t)1 << (8u * T)) - 1;
+                        tail = v << (8u * (8u - T));   // right-aligned
+                    }
+                    const uint64_t slot = rec + (uint64_t)(n + r) * 32;   // (n + r < maxFrames)
+                    st16(slot, make_uint4((uint32_t)a, kRowOk | (type << 8) | ((h + inner) << 16) | (T << 24), flow,
+                                          num));
+                    st16(slot + 16, make_uint4(D, head, (uint32_t)tail, (uint32_t)(tail >> 32)));
+                    frames = r + 1;
+                    isLast = p + total >= C;
+                    kind = kHopExit;
+                    pos = a + total;
+                }
+            }
+            if (isLast) {
+                last[0] = kind;
+                last[1] = frames;
+                last[2] = (uint32_t)pos;
+                last[3] = (uint32_t)(pos >> 32);
+            }
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (unsigned s = 32; s >= 1; s >>= 1) {
+            const uint32_t o = __shfl_xor(morePos, s);
+            morePos = o < morePos ? o : morePos;
+        }
+        if (morePos < C) {   // (the frames of rank below room were all stored)
+            n = maxFrames;
+            flags |= kPackedMore;
+            next = base + morePos;
+            open = false;
+        } else {
+            const uint32_t kind = last[0];
+            const uint64_t pos = pack64(last[2], last[3]);
+            n += last[1];
+            if (kind == kHopExit) {
+                at = pos;
+            } else {
+                flags |= kind == kHopPartial ? kStreamPartial : kind == kHopBad ? kPackedMalformed : 0u;
+                next = kind == kHopEnd ? end : pos;
+                open = false;
+            }
+        }
+        wave_lds_sync();   // (the next chunk's stage overwrites what was read here)
+    }
+    if (lane == 0) {
+        *reinterpret_cast<GMEM uint32_t*>(words + k * 4) = n | flags;
+        *reinterpret_cast<GMEM uint32_t*>(nexts + k * 4) = next < 0xffffffffull ? (uint32_t)next : 0xffffffffu;
+    }
+    // the zeros between the next words and the next 16-byte boundary: every byte is written by every scan
+    if (k == (uint64_t)count - 1 && lane >= 1 && lane < 4 && k + lane < (((uint64_t)count + 3) & ~(uint64_t)3))
+        *reinterpret_cast<GMEM uint32_t*>(nexts + (k + lane) * 4) = 0;
+}
+
+// ---------------------------------------------------------------------------
 // Duplex row walk (k_ackwalk, ops.h kRowTruncated)
 //
 // k_walk for the rows of a bidirectional flow (frames.h ack_walk is the
@@ -5366,7 +5681,8 @@ void harvest_timing(bool all)
             break;
         // (a synchronised codec stream says nothing about the gather stream)
         if (all && (ev.kind == kBeScan || ev.kind == kBeWalk || ev.kind == kBeAckWalk || ev.kind == kBeRowsum ||
-                    ev.kind == kBeCompact || ev.kind == kBeRowsum2 || ev.kind == kBeSlots))
+                    ev.kind == kBeCompact || ev.kind == kBeRowsum2 || ev.kind == kBeSlots ||
+                    ev.kind == kBeStreamWalk))
             (void)hipEventSynchronize(ev.b);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.a, ev.b);
@@ -6342,6 +6658,51 @@ bool be_dense_rows(const void* rows, uint64_t stride, const uint32_t* lens, uint
                            dim3(kCompactThreads), 0, g_gatherStream, out, scratch, count, maxFrames, maxRecords);
     }
     if (hipMemcpyAsync(hostOut, devStage, (size_t)dense_bytes(count, maxRecords), hipMemcpyDeviceToHost,
+                       g_gatherStream) != hipSuccess ||
+        hipEventRecord(l, g_gatherStream) != hipSuccess) {
+        be_mark_release(l);
+        return false;
+    }
+    *landed = l;
+    return true;
+}
+
+bool be_stream_rows(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends, uint32_t count,
+                    uint32_t maxFrames, uint32_t maxRecords, void* devStage, void* hostOut, void** packed,
+                    void** landed)
+{
+    bind_device();
+    *packed = *landed = nullptr;
+    hipEvent_t p = take_mark(), l = take_mark();
+    if (!p || !l) {
+        be_mark_release(p);
+        be_mark_release(l);
+        return false;
+    }
+    const uint64_t out = (uint64_t)(uintptr_t)devStage;
+    const uint64_t scratch = out + streams_scratch_offset(count, maxRecords);
+    {
+        Timed t(kBeStreamWalk, g_gatherStream);
+        hipLaunchKernelGGL(k_streamwalk, dim3((count + kStreamWaves - 1) / kStreamWaves), dim3(kStreamWalkThreads), 0,
+                           g_gatherStream, (uint64_t)(uintptr_t)rows, stride, starts, ends, count, maxFrames, scratch,
+                           out + 16, out + streams_next_offset(count, maxRecords));
+    }
+    // (the rows have been read: what follows works on the staging area alone)
+    if (hipEventRecord(p, g_gatherStream) != hipSuccess)
+        return false;
+    *packed = p;
+    {
+        Timed t(kBeRowsum, g_gatherStream);
+        hipLaunchKernelGGL(k_rowsum, dim3(1), dim3(kRowsumThreads), 0, g_gatherStream, out, count, maxFrames,
+                           maxRecords);
+    }
+    {
+        Timed t(kBeCompact, g_gatherStream);
+        const uint64_t lanes = 2 * (uint64_t)maxRecords;
+        hipLaunchKernelGGL(k_compact, dim3((uint32_t)((lanes + kCompactThreads - 1) / kCompactThreads)),
+                           dim3(kCompactThreads), 0, g_gatherStream, out, scratch, count, maxFrames, maxRecords);
+    }
+    if (hipMemcpyAsync(hostOut, devStage, (size_t)streams_bytes(count, maxRecords), hipMemcpyDeviceToHost,
                        g_gatherStream) != hipSuccess ||
         hipEventRecord(l, g_gatherStream) != hipSuccess) {
         be_mark_release(l);

@@ -894,11 +894,13 @@ SIAMESE_EXPORT long long sgpu_frames_scan_dense(const void* deviceRows, size_t s
                                                          count ? maxRecords : 0, pinnedOut);
 }
 
-SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders, unsigned decoderCount,
-                                                    const void* heads, unsigned maxFrames, unsigned maxRecords,
-                                                    const void* deviceRows, size_t stride, unsigned count,
-                                                    SiameseResult* results, unsigned* rowsOut,
-                                                    unsigned* acceptedOut)
+namespace {
+// sgpu_frames_recv_dense and, with the next words behind the dense part (streams) and consumedOut,
+// sgpu_frames_recv_streams
+SiameseResult recv_dense_rows(const SgpuDecoder* decoders, unsigned decoderCount, const void* heads,
+                              unsigned maxFrames, unsigned maxRecords, const void* deviceRows, size_t stride,
+                              unsigned count, SiameseResult* results, bool streams, unsigned* consumedOut,
+                              unsigned* rowsOut, unsigned* acceptedOut)
 {
     if (rowsOut)
         *rowsOut = 0;
@@ -907,7 +909,7 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders,
     *acceptedOut = 0;
     if (!rowsOut || !rows_ok(deviceRows, stride, count) || ((!decoders || !heads) && count > 0) ||
         ((uintptr_t)heads & 3) || maxFrames < 1 || maxFrames > kPackedMaxFrames ||
-        (count > 0 && !dense_ok(count, maxFrames, maxRecords)))
+        (count > 0 && !dense_ok(count, maxFrames, maxRecords)) || (streams && !consumedOut && count > 0))
         return Siamese_InvalidInput;
     if (count == 0)
         return Siamese_Success;
@@ -919,6 +921,7 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders,
     const uint8_t* words = base + 16;
     const uint8_t* starts = words + (size_t)count * 4;
     const uint8_t* recs = base + (size_t)dense_records_offset(count);
+    const uint8_t* nextWords = streams ? base + (size_t)streams_next_offset(count, maxRecords) : nullptr;
     uint32_t info[4];
     std::memcpy(info, base, sizeof(info));
     const uint32_t W = info[1], c = info[2];
@@ -946,6 +949,21 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders,
             n = 0;
             malformed = true;
         }
+        uint32_t resume = 0;
+        if (nextWords) {
+            // where the row's next scan starts: within the row, and not before the end of its last record
+            std::memcpy(&resume, nextWords + (size_t)k * 4, 4);
+            uint64_t least = 0;
+            if (n > 0) {
+                PackedHead h;
+                std::memcpy(&h, recs + ((size_t)at + n - 1) * sizeof(h), sizeof(h));
+                least = (uint64_t)h.offset + h.headerBytes + h.dataBytes;
+            }
+            if (resume > stride || resume < least) {
+                forged = true;
+                break;
+            }
+        }
         for (unsigned j = 0; j < n; ++j) {
             PackedHead h;
             std::memcpy(&h, recs + ((size_t)at + j) * sizeof(h), sizeof(h));
@@ -960,6 +978,8 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders,
         }
         if (malformed && status == Siamese_Success)   // (the frame the walk stopped at has no slot here)
             status = Siamese_InvalidInput;
+        if (nextWords)
+            consumedOut[k] = resume;
         at = next;
     }
     if (!forged && at != W)
@@ -967,6 +987,57 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders,
     *rowsOut = k;   // c, unless the table stopped the routing before it
     *acceptedOut = accepted;
     return forged ? Siamese_InvalidInput : status;
+}
+} // namespace
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                    const void* heads, unsigned maxFrames, unsigned maxRecords,
+                                                    const void* deviceRows, size_t stride, unsigned count,
+                                                    SiameseResult* results, unsigned* rowsOut,
+                                                    unsigned* acceptedOut)
+{
+    return recv_dense_rows(decoders, decoderCount, heads, maxFrames, maxRecords, deviceRows, stride, count, results,
+                           false, nullptr, rowsOut, acceptedOut);
+}
+
+static_assert(SGPU_STREAM_PARTIAL == kStreamPartial && !(SGPU_STREAM_PARTIAL & (kPackedCountMask | kPackedMore |
+                                                                                 kPackedMalformed)),
+              "the stream scan's row word");
+
+SIAMESE_EXPORT size_t sgpu_frames_streams_bytes(unsigned count, unsigned maxRecords)
+{
+    return sgpu_frames_dense_bytes(count, maxRecords) ? (size_t)streams_bytes(count, maxRecords) : 0;
+}
+
+SIAMESE_EXPORT size_t sgpu_frames_streams_next(unsigned count, unsigned maxRecords)
+{
+    return sgpu_frames_dense_bytes(count, maxRecords) ? (size_t)streams_next_offset(count, maxRecords) : 0;
+}
+
+SIAMESE_EXPORT long long sgpu_frames_scan_streams(const void* deviceRows, size_t stride, const unsigned* deviceStarts,
+                                                  const unsigned* deviceEnds, unsigned count, unsigned maxFrames,
+                                                  unsigned maxRecords, void* pinnedOut)
+{
+    if (!g_batchReady || !rows_ok(deviceRows, stride, count) || ((uintptr_t)deviceStarts & 3) ||
+        ((uintptr_t)deviceEnds & 3) || ((uintptr_t)pinnedOut & 15) || (!pinnedOut && count > 0) || maxFrames < 1 ||
+        maxFrames > kPackedMaxFrames || packed_bytes(count, maxFrames) > ((uint64_t)1 << 32))
+        return -1;
+    // (count == 0 admits no maxRecords >= maxFrames: its ticket is complete and nothing is written)
+    if (count > 0 &&
+        (!dense_ok(count, maxFrames, maxRecords) || streams_bytes(count, maxRecords) >= ((uint64_t)1 << 32)))
+        return -1;
+    return (long long)Engine::global()->stream_rows_async(deviceRows, stride, deviceStarts, deviceEnds, count,
+                                                          maxFrames, count ? maxRecords : 0, pinnedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_streams(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                      const void* heads, unsigned maxFrames, unsigned maxRecords,
+                                                      const void* deviceRows, size_t stride, unsigned count,
+                                                      SiameseResult* results, unsigned* consumedOut,
+                                                      unsigned* rowsOut, unsigned* acceptedOut)
+{
+    return recv_dense_rows(decoders, decoderCount, heads, maxFrames, maxRecords, deviceRows, stride, count, results,
+                           true, consumedOut, rowsOut, acceptedOut);
 }
 
 SIAMESE_EXPORT SiameseResult sgpu_encoder_pack_frames(SgpuEncoder encoder, unsigned flow, unsigned firstPacketNum,
@@ -1420,7 +1491,7 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
     const Engine* e = Engine::global();
-    const uint64_t v[42] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[43] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
@@ -1432,8 +1503,8 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
                             e->rows_shape(0), e->rows_shape(1), e->rows_shape(2), e->rows_shape(3),
                             e->rows_shape(4), be_exec_stage_cap(),
                             e->denses(),  s.gePivoted,   s.geSingular,
-                            e->duplex_denses(), e->solves_flagged(), e->solves_cut()};
-    for (unsigned k = 0; k < count && k < 42; ++k)
+                            e->duplex_denses(), e->solves_flagged(), e->solves_cut(), e->streams()};
+    for (unsigned k = 0; k < count && k < 43; ++k)
         out[k] = v[k];
 }
 

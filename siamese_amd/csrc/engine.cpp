@@ -3168,10 +3168,11 @@ int64_t Engine::gather_async_framed(unsigned count, const void* const* srcs, con
 // scan_rows_async (maxFrames == 0: k_scan) and walk_rows_async (k_walk)
 // and duplex_rows_async (ackSlots != 0: k_ackwalk) and dense_rows_async
 // (maxRecords != 0: k_walkd, k_rowsum and k_compact) and duplex_dense_rows_async (maxRecords != 0 and
-// ackSlots != 0: k_ackwalkd, k_rowsum2, k_compact and k_slots)
+// ackSlots != 0: k_ackwalkd, k_rowsum2, k_compact and k_slots) and stream_rows_async (streams: k_streamwalk,
+// k_rowsum and k_compact, with lens as the rows' ends)
 int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
                            unsigned maxFrames, void* pinnedOut, unsigned ackSlots, unsigned ackBytes,
-                           unsigned maxRecords, unsigned maxAcks)
+                           unsigned maxRecords, unsigned maxAcks, bool streams, const uint32_t* starts)
 {
     if (failed())
         return -1;
@@ -3185,8 +3186,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     // the records take the slot's packing area (the dense scans' scratch areas behind their output); a scan
     // uploads no descriptors
     const bool duplexDense = maxRecords && ackSlots;
-    const size_t total = duplexDense ? (size_t)duplex_dense_stage_bytes(count, maxFrames, ackSlots, maxRecords,
-                                                                        maxAcks, ackBytes)
+    const size_t total = streams     ? (size_t)streams_stage_bytes(count, maxFrames, maxRecords)
+                         : duplexDense ? (size_t)duplex_dense_stage_bytes(count, maxFrames, ackSlots, maxRecords,
+                                                                          maxAcks, ackBytes)
                          : maxRecords ? (size_t)dense_stage_bytes(count, maxFrames, maxRecords)
                          : ackSlots  ? (size_t)duplex_bytes(count, maxFrames, ackSlots, ackBytes)
                          : maxFrames ? (size_t)packed_bytes(count, maxFrames)
@@ -3203,8 +3205,10 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     if (!g.stage)
         return -1;
     void* packed = nullptr;
-    if (!(duplexDense ? be_duplex_dense_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, maxRecords,
-                                             maxAcks, g.stage, pinnedOut, &packed, &g.landed)
+    if (!(streams     ? be_stream_rows(rows, stride, starts, lens, count, maxFrames, maxRecords, g.stage, pinnedOut,
+                                       &packed, &g.landed)
+          : duplexDense ? be_duplex_dense_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, maxRecords,
+                                               maxAcks, g.stage, pinnedOut, &packed, &g.landed)
           : maxRecords ? be_dense_rows(rows, stride, lens, count, maxFrames, maxRecords, g.stage, pinnedOut, &packed,
                                       &g.landed)
           : ackSlots  ? be_ackwalk_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, g.stage, pinnedOut,
@@ -3215,7 +3219,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
         return -1;
     }
     g.ticket = ticket;
-    if (duplexDense)
+    if (streams)
+        streams_.fetch_add(count, std::memory_order_relaxed);
+    else if (duplexDense)
         duplexDenses_.fetch_add(count, std::memory_order_relaxed);
     else if (maxRecords)
         denses_.fetch_add(count, std::memory_order_relaxed);

@@ -813,6 +813,18 @@ public:
     {
         return rows_async(rows, stride, lens, count, maxFrames, pinnedOut, ackSlots, ackBytes, maxRecords, maxAcks);
     }
+    /// The dense scan for rows that are byte streams: row bytes [starts[k],
+    /// ends[k]) walked with a cut-off last frame reported as partial, and behind
+    /// the dense output one next word per row, streams_bytes(count, maxRecords) in
+    /// all, into pinnedOut (k_streamwalk, k_rowsum and k_compact,
+    /// sgpu_frames_scan_streams).  starts, ends: the rows' words in device memory,
+    /// or null.  The same gather slots and tickets, and maxRecords as
+    /// dense_rows_async's.
+    int64_t stream_rows_async(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends,
+                              unsigned count, unsigned maxFrames, unsigned maxRecords, void* pinnedOut)
+    {
+        return rows_async(rows, stride, ends, count, maxFrames, pinnedOut, 0, 0, maxRecords, 0, true, starts);
+    }
     /// Wait until gather `ticket` and every earlier one have landed.
     bool gather_wait(int64_t ticket);
     /// Host -> device copy on the staging stream, issued now; every later
@@ -987,7 +999,7 @@ private:
     bool gather_land(GatherSlot& g);
     int64_t rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count, unsigned maxFrames,
                        void* pinnedOut, unsigned ackSlots = 0, unsigned ackBytes = 0, unsigned maxRecords = 0,
-                       unsigned maxAcks = 0);
+                       unsigned maxAcks = 0, bool streams = false, const uint32_t* starts = nullptr);
     // rows scanned by the packed scan, counted when the scan is queued (sgpu_engine_stats_ex [24]); kept
     // here, behind every other member, and not in EngineStats, whose size every submission's counters share
     std::atomic<uint64_t> walks_{0};
@@ -1017,6 +1029,8 @@ private:
     // counted by the completion (DecoderCore::complete_solve; [40], [41]); here for the same reason
     std::atomic<uint64_t> solvesFlagged_{0};
     std::atomic<uint64_t> solvesCut_{0};
+    // rows scanned by the stream scan, counted as walks_ ([42]); here for the same reason
+    std::atomic<uint64_t> streams_{0};
 
 public:
     uint64_t rows_shape(unsigned k) const { return rowsShape_[k].load(std::memory_order_relaxed); }
@@ -1025,6 +1039,7 @@ public:
     uint64_t concats() const { return concats_.load(std::memory_order_relaxed); }
     uint64_t denses() const { return denses_.load(std::memory_order_relaxed); }
     uint64_t duplex_denses() const { return duplexDenses_.load(std::memory_order_relaxed); }
+    uint64_t streams() const { return streams_.load(std::memory_order_relaxed); }
     uint64_t solves_flagged() const { return solvesFlagged_.load(std::memory_order_relaxed); }
     uint64_t solves_cut() const { return solvesCut_.load(std::memory_order_relaxed); }
     void count_solve_outcome(bool flagged, bool cut)

@@ -258,6 +258,99 @@ inline uint32_t row_walk(const uint8_t* row, uint64_t stride, const uint32_t* le
     return n;
 }
 
+/// What k_streamwalk computes for one row of a byte stream (ops.h kStreamPartial,
+/// sgpu_frames_scan_streams / sgpu_frames_recv_streams): row[0, stride) in host
+/// memory, out = the row's maxFrames records, *next = the row offset from which
+/// the row's next scan must start.  start > end or end > stride is a malformed
+/// row without records and *next = min(start, stride).  Otherwise row[start,
+/// end) is walked as row_walk walks row[0, end), with one more outcome: a frame
+/// at `at` that the left = end - at bytes do not hold whole -- left is less than
+/// the w bytes its first byte announces for the prefix, or the prefix gives L >=
+/// 1 with w + L > left -- ends the walk with kStreamPartial when nothing that is
+/// already there can make it invalid, and with kPackedMalformed when something
+/// can: w + L > stride (no row will ever hold it), a type byte that is present
+/// and above kFrameRecovery, a type byte that is present with L <= the type's
+/// inner header, or an original whose three PacketNum bytes are all present and
+/// exceed SIAMESE_PACKET_NUM_MAX.  *next is `end` when only zero bytes were left,
+/// and otherwise the offset of the byte the walk stopped at: the non-zero byte
+/// behind the maxFrames-th record (kPackedMore), or the first byte of the frame
+/// that is partial or malformed.  (A next word has 32 bits: an `end` of 4 GiB,
+/// which only a null end array with that stride gives, is stated as 2^32 - 1.)
+/// Records past the last accepted frame are zero.  Returns the row word.
+inline uint32_t stream_walk(const uint8_t* row, uint64_t stride, uint64_t start, uint64_t end, uint32_t maxFrames,
+                            PackedHead* out, uint32_t* next)
+{
+    std::memset(out, 0, (size_t)maxFrames * sizeof(*out));
+    if (start > end || end > stride) {
+        *next = (uint32_t)(start < stride ? start : stride);
+        return kPackedMalformed;
+    }
+    uint64_t at = start;
+    uint32_t n = 0;
+    while (at < end) {
+        if (row[at] == 0) {
+            ++at;
+            continue;
+        }
+        *next = (uint32_t)at;
+        if (n == maxFrames)
+            return n | kPackedMore;
+        const uint64_t left = end - at;
+        unsigned length = 0;
+        const int h = read_length_prefix(row + at, left < 4 ? (unsigned)left : 4u, &length);
+        if (h < 1)
+            return n | kStreamPartial;   // (the prefix itself is cut off)
+        if (length < 1)
+            return n | kPackedMalformed;
+        const uint8_t* f = row + at + h;   // type, flow, PacketNum: the first left - h of them are there
+        if ((uint64_t)h + length > left) {
+            const uint64_t have = left - h;
+            bool never = (uint64_t)h + length > stride;
+            if (have >= 1) {
+                const unsigned inner = f[0] == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+                never = never || f[0] > kFrameRecovery || length <= inner;
+                if (f[0] == kFrameOriginal && have >= kFrameOriginalInner)
+                    never = never || (f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16)) > SIAMESE_PACKET_NUM_MAX;
+            }
+            return n | (never ? kPackedMalformed : kStreamPartial);
+        }
+        PackedHead r;
+        std::memset(&r, 0, sizeof(r));
+        r.offset = (uint32_t)at;
+        r.status = kRowOk;
+        r.type = f[0];
+        const unsigned inner = r.type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+        if (r.type > kFrameRecovery || length <= inner)
+            return n | kPackedMalformed;
+        r.headerBytes = (uint8_t)(h + inner);
+        r.flow = f[1] | ((uint32_t)f[2] << 8) | ((uint32_t)f[3] << 16);
+        r.packetNum = r.type == kFrameOriginal ? f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) : 0;
+        r.dataBytes = length - inner;
+        r.tailBytes = r.type == kFrameRecovery ? (uint8_t)(r.dataBytes < 8 ? r.dataBytes : 8) : 0;
+        if (!packed_head_valid(r, end))
+            return n | kPackedMalformed;
+        if (r.type == kFrameRecovery) {
+            const uint8_t* data = row + at + r.headerBytes;
+            std::memcpy(r.head, data, r.dataBytes < 4 ? r.dataBytes : 4);
+            std::memcpy(r.tail + 8 - r.tailBytes, data + r.dataBytes - r.tailBytes, r.tailBytes);
+        }
+        out[n++] = r;
+        at += (uint64_t)h + length;
+    }
+    *next = end < 0xffffffffu ? (uint32_t)end : 0xffffffffu;   // (end = stride = 4 GiB: the row's last byte, a zero)
+    return n;
+}
+
+/// The next words behind a stream scan's dense part (ops.h streams_bytes): out =
+/// streams_bytes(count, maxRecords) bytes whose first dense_bytes(count,
+/// maxRecords) dense_compact has written.
+inline void streams_put_next(const uint32_t* next, uint32_t count, uint32_t maxRecords, uint8_t* out)
+{
+    uint8_t* at = out + (size_t)streams_next_offset(count, maxRecords);
+    std::memset(at, 0, (size_t)(streams_bytes(count, maxRecords) - streams_next_offset(count, maxRecords)));
+    std::memcpy(at, next, (size_t)count * 4);
+}
+
 /// What k_rowsum and k_compact compute from the walk's output (ops.h
 /// dense_bytes states the layout, sgpu_frames_scan_dense / sgpu_frames_recv_dense
 /// use it): words = the count row words, rowRecs = maxFrames records per row as

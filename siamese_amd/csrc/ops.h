@@ -779,6 +779,42 @@ constexpr uint64_t duplex_dense_stage_bytes(uint64_t count, uint64_t maxFrames, 
            ((count * 4 + 15) & ~(uint64_t)15);
 }
 
+/// Byte-stream rows (k_streamwalk, k_rowsum and k_compact,
+/// sgpu_frames_scan_streams): row k is a connection's receive buffer whose bytes
+/// [start_k, end_k) hold frames back to back, the last of which may still be
+/// arriving.  The output is the dense layout above (dense_bytes) and behind it
+///   count next words | zeros to the next 16-byte boundary
+/// where row word k may carry kStreamPartial (the walk stopped at a frame the
+/// data does not yet hold whole) and next_k is the row offset from which the
+/// row's next scan must start (frames.h stream_walk states the walk).  A
+/// record's offset is relative to the row's first byte, not to start_k.
+///
+/// On the device the walk takes one wave per row, kStreamWalkThreads / 64 rows
+/// per workgroup, and consumes the row in chunks of kStreamChunk bytes (64 lanes
+/// x 16 bytes) staged in LDS with a 16-byte halo; its per-row scratch records lie
+/// behind the output as the dense scan's do (streams_scratch_offset).
+constexpr uint32_t kStreamPartial = 0x20000000u;
+constexpr uint32_t kStreamChunk = 1024;
+constexpr uint32_t kStreamWalkThreads = 256;
+/// Where a stream scan's next words start, its output's bytes, and where the
+/// device's scratch records start in the staging area.
+constexpr uint64_t streams_next_offset(uint64_t count, uint64_t maxRecords)
+{
+    return dense_bytes(count, maxRecords);   // (a multiple of 16)
+}
+constexpr uint64_t streams_bytes(uint64_t count, uint64_t maxRecords)
+{
+    return streams_next_offset(count, maxRecords) + ((count * 4 + 15) & ~(uint64_t)15);
+}
+constexpr uint64_t streams_scratch_offset(uint64_t count, uint64_t maxRecords)
+{
+    return streams_bytes(count, maxRecords);
+}
+constexpr uint64_t streams_stage_bytes(uint64_t count, uint64_t maxFrames, uint64_t maxRecords)
+{
+    return streams_scratch_offset(count, maxRecords) + count * maxFrames * sizeof(PackedHead);
+}
+
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)
 /// Solves with more rows than this stage 256-byte tiles (16 lanes x 16 bytes

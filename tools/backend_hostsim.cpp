@@ -819,6 +819,26 @@ bool be_duplex_dense_rows(const void* rows, uint64_t stride, const uint32_t* len
     return true;
 }
 
+// k_streamwalk, k_rowsum and k_compact (ops.h streams_bytes): frames.h
+// stream_walk per row into the scratch area, then frames.h dense_compact and
+// the next words.
+bool be_stream_rows(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends, uint32_t count,
+                    uint32_t maxFrames, uint32_t maxRecords, void* devStage, void* hostOut, void** packed,
+                    void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    uint8_t* out = static_cast<uint8_t*>(devStage);
+    PackedHead* scratch = reinterpret_cast<PackedHead*>(out + (size_t)streams_scratch_offset(count, maxRecords));
+    std::vector<uint32_t> words(count), next(count);
+    for (uint32_t k = 0; k < count; ++k)
+        words[k] = stream_walk(static_cast<const uint8_t*>(rows) + (uint64_t)k * stride, stride, starts ? starts[k] : 0,
+                               ends ? ends[k] : stride, maxFrames, scratch + (size_t)k * maxFrames, &next[k]);
+    dense_compact(words.data(), scratch, count, maxFrames, maxRecords, out);
+    streams_put_next(next.data(), count, maxRecords, out);
+    std::memcpy(hostOut, devStage, (size_t)streams_bytes(count, maxRecords));
+    return true;
+}
+
 // HOSTSIM_FAIL_SYNC=N: the N-th be_sync (1-based) and every later one
 // report a device fault (tests of the sticky Disabled path).
 bool be_sync()
