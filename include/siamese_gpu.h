@@ -741,9 +741,9 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_dense(const SgpuDecoder* decoders,
     maxRecords), count uint32 next words and zeros up to the next 16-byte
     boundary.  Every byte is written by every scan.  A record's Offset is
     relative to the row's first byte, not to start.  Still not offered: a ring
-    that wraps around inside a row (compact it, or map it twice), ack frames in
-    stream rows (the duplex scans take those), and more than 256 frames per row
-    and scan (resume from the next word).
+    that wraps around inside a row (compact it, or map it twice) and more than
+    256 frames per row and scan (resume from the next word).  Ack frames in
+    stream rows are malformed here; sgpu_frames_scan_duplex_streams takes them.
 */
 #define SGPU_STREAM_PARTIAL 0x20000000u  /* row word: the walk stopped at a frame the data does not yet hold whole */
 
@@ -1187,6 +1187,127 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* de
                                                            SiameseResult* results /* maxRecords, optional */,
                                                            unsigned* nextExpectedOut /* maxRecords, optional */,
                                                            unsigned* rowsOut, unsigned* acceptedOut);
+/*
+    Duplex rows that are byte streams.  A stream transport is bidirectional, and
+    ARQ runs over it: a connection's receive buffer in device memory holds the
+    peer's data frames and its acknowledgements back to back, and the last frame
+    is usually still arriving.  The duplex stream scan is the dense duplex scan
+    over row bytes [start, end), with sgpu_frames_scan_streams' partial frame and
+    next words:
+
+        bytes  = sgpu_frames_duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes);   // pinned
+        for (;;) {
+            // the transport has advanced ends[k]; starts[k] is where row k's last scan stopped
+            ticket = sgpu_frames_scan_duplex_streams(rows, stride, starts, ends, count, maxFrames, ackSlots,
+                                                     ackBytes, maxRecords, maxAcks, out);
+            sgpu_gather_wait(ticket);
+            sgpu_frames_recv_duplex_streams(decoders, nd, encoders, ne, out, maxFrames, ackSlots, ackBytes,
+                                            maxRecords, maxAcks, rows, stride, count, results, nextExpected,
+                                            consumed, &rowsDone, &accepted);
+            // consumed[k], k < rowsDone, is row k's next start: write it back to starts[k]
+            // (rows from rowsDone on keep their old starts and are scanned again);
+            // answer with sgpu_decoders_ack_frames and sgpu_encoder_retransmit_frames as in the datagram loop
+        }
+
+    out holds sgpu_frames_scan_duplex_dense's layout, all
+    sgpu_frames_duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes) bytes of
+    it -- info {T, W, c, WA}, both start tables, records and slots, rows all or
+    nothing over both budgets -- and then, at sgpu_frames_duplex_streams_next(...),
+    count uint32 next words and zeros up to the next 16-byte boundary.  Every byte
+    is written by every scan.  A record's Offset is relative to the row's first
+    byte, not to start.  A row word may carry SGPU_STREAM_PARTIAL_DUPLEX, which
+    has a bit of its own: SGPU_STREAM_PARTIAL shares SGPU_PACKED_ACKS_DROPPED's
+    bit and keeps its value and meaning in sgpu_frames_scan_streams, and a duplex
+    stream row can drop an ack and stop at a partial frame in one scan.  Acks
+    are numbered within the scan: the row's a-th ack of this scan has PacketNum
+    a and slot a.  An ack dropped for lack of a slot (SGPU_ROW_TRUNCATED) lies
+    behind the row's next word and is not seen again by the next scan; a caller
+    that wants it scans the row again from that record's Offset with more slots.
+    Still not offered: a ring that wraps around inside a row, more than 256
+    frames per row and scan (resume from the next word), and a walk that stops
+    at an ack without a slot.
+*/
+#define SGPU_STREAM_PARTIAL_DUPLEX 0x10000000u  /* row word of a duplex stream scan: stopped at a frame not yet whole */
+
+/// Bytes of a duplex stream scan's output (0 where sgpu_frames_duplex_dense_bytes is 0).
+SIAMESE_EXPORT size_t sgpu_frames_duplex_streams_bytes(unsigned count, unsigned maxRecords, unsigned maxAcks,
+                                                       unsigned ackBytes);
+/// Byte offset of the next words in a duplex stream scan's output:
+/// sgpu_frames_duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes).
+SIAMESE_EXPORT size_t sgpu_frames_duplex_streams_next(unsigned count, unsigned maxRecords, unsigned maxAcks,
+                                                      unsigned ackBytes);
+/// Scan `count` duplex byte-stream rows into pinnedOut (pinned, 16-byte aligned,
+/// sgpu_frames_duplex_streams_bytes): a gather with
+/// sgpu_frames_scan_duplex_dense's ticket, ordering and lifetime contract, its
+/// rows, stride, maxFrames, ackSlots, ackBytes, maxRecords and maxAcks.
+///
+/// Row k is walked over its bytes [start, end), start = deviceStarts ?
+/// deviceStarts[k] : 0 and end = deviceEnds ? deviceEnds[k] : stride (uint32
+/// arrays in device memory, 4-byte aligned; byte offsets from the row's first
+/// byte, at any alignment), as sgpu_frames_scan_duplex walks a row from 0: zero
+/// bytes where a frame would start are skipped, and a frame of type 0, 1 or 2 is
+/// accepted under that scan's rules.  The row's a-th ack, counted within this
+/// scan, has PacketNum a; slot a receives the first min(D, ackBytes) bytes of
+/// its message; with a >= ackSlots or D > ackBytes its Status is
+/// SGPU_ROW_TRUNCATED, the word gets SGPU_PACKED_ACKS_DROPPED and the walk goes
+/// on behind it.  Row word k and next word k say how the walk ended:
+///   - start > end or end > stride: SGPU_PACKED_MALFORMED, no records, no acks,
+///     next = min(start, stride);
+///   - only zero bytes were left: the count n, next = end;
+///   - n == maxFrames and a non-zero byte is left: n | SGPU_PACKED_MORE, next =
+///     that byte's offset;
+///   - a partial frame at `at`: n | SGPU_STREAM_PARTIAL_DUPLEX, next = at.  With
+///     left = end - at, the frame is partial when its first byte announces a
+///     prefix of w bytes and left < w, or the prefix gives L >= 1 and w + L >
+///     left, and nothing that is present is wrong already.  A partial ack
+///     writes no slot, gets no record and does not count as one of the row's
+///     acks;
+///   - a frame at `at` that is whole and fails a rule (L == 0 included), or that
+///     is cut off and can never become valid -- w + L > stride, a type byte that
+///     is present and above 2, a type byte that is present with L not above the
+///     type's inner header (7, 4, 4), an original whose three PacketNum bytes are
+///     present and exceed SIAMESE_PACKET_NUM_MAX -- : n | SGPU_PACKED_MALFORMED,
+///     next = at.
+/// A word may carry SGPU_PACKED_ACKS_DROPPED together with any one of the three
+/// stop flags.  Next word k is written for every row, also for k >= c.  (With a
+/// null deviceEnds and a stride of 4 GiB, next = end is stated as 2^32 - 1.)
+/// With start 0 and no partial frame the first sgpu_frames_duplex_dense_bytes
+/// bytes are sgpu_frames_scan_duplex_dense's on the same rows with lens = ends
+/// and the same sizes, byte for byte.  Nothing outside [row, row + stride) and
+/// the row's two words is read, and the bytes before start and from end on --
+/// stale ring content -- influence no output bit.
+///
+/// Returns -1, with nothing queued, where sgpu_frames_scan_duplex_dense does, for
+/// a misaligned deviceStarts or deviceEnds and for an output of 4 GiB or more.
+/// count == 0 returns a valid ticket that is already complete, and nothing is
+/// written.
+SIAMESE_EXPORT long long sgpu_frames_scan_duplex_streams(const void* deviceRows, size_t stride,
+                                                         const unsigned* deviceStarts, const unsigned* deviceEnds,
+                                                         unsigned count, unsigned maxFrames, unsigned ackSlots,
+                                                         unsigned ackBytes, unsigned maxRecords, unsigned maxAcks,
+                                                         void* pinnedOut);
+/// Host only: sgpu_frames_recv_duplex_dense for a duplex stream scan's output,
+/// with the same routing, results, nextExpectedOut, *rowsOut and *acceptedOut
+/// and the same copies and checks of info, words, both start tables, records and
+/// slots.  A word may carry SGPU_STREAM_PARTIAL_DUPLEX, which is no error and
+/// adds nothing to the return value; SGPU_PACKED_MALFORMED contributes
+/// Siamese_InvalidInput after the row's good frames, as there.  For a row k < c,
+/// next[k] <= stride and, when the row has records, next[k] >= the end of its
+/// last record are checked before any of the row's records are routed: a next
+/// word that fails stops the routing as a start that fails does.  consumedOut[k]
+/// = next[k] for k < *rowsOut; the entries from *rowsOut on are left untouched
+/// (scan those rows again from their old starts).  Arguments are refused as in
+/// sgpu_frames_recv_duplex_dense, and a null consumedOut with count > 0.
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_streams(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                             const SgpuEncoder* encoders, unsigned encoderCount,
+                                                             const void* heads, unsigned maxFrames,
+                                                             unsigned ackSlots, unsigned ackBytes,
+                                                             unsigned maxRecords, unsigned maxAcks,
+                                                             const void* deviceRows, size_t stride, unsigned count,
+                                                             SiameseResult* results /* maxRecords, optional */,
+                                                             unsigned* nextExpectedOut /* maxRecords, optional */,
+                                                             unsigned* consumedOut /* count, host */,
+                                                             unsigned* rowsOut, unsigned* acceptedOut);
 
 /// Device timing of flushed work since the last reset (milliseconds).
 SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* totalMs);
@@ -1206,8 +1327,10 @@ SIAMESE_EXPORT void sgpu_timing(int enable, int reset, double* execMs, double* t
 /// counted under [8]), [17] k_rowsum2 and [18] k_slots
 /// (sgpu_frames_scan_duplex_dense, likewise; its walk is counted under [12] and
 /// its record copy under [16]), [19] k_streamwalk (sgpu_frames_scan_streams,
-/// likewise; its k_rowsum and k_compact are counted under [15] and [16]); count
-/// entries at most.
+/// likewise; its k_rowsum and k_compact are counted under [15] and [16]), [20]
+/// k_ackstreamwalk (sgpu_frames_scan_duplex_streams, likewise; its k_rowsum2,
+/// k_compact and k_slots are counted under [17], [16] and [18]); count entries
+/// at most.
 SIAMESE_EXPORT void sgpu_timing_kernels(double* msOut, unsigned count);
 /// Engine counters (15 values): flushes, launches, ops, terms, solves,
 /// ingests, upload bytes, algorithmic op bytes, algorithmic output bytes,
@@ -1256,8 +1379,9 @@ SIAMESE_EXPORT void sgpu_engine_stats(uint64_t* out15);
 /// the exact sweeps redid them (inconsistent recovery data; always 0 where no
 /// product solve runs), and [41] the solves that stopped at an invalid
 /// recovered length prefix (the decoder is disabled, as the reference's), then
-/// [42] the rows scanned by sgpu_frames_scan_streams, counted as [36]; count
-/// entries at most.
+/// [42] the rows scanned by sgpu_frames_scan_streams, counted as [36], then [43]
+/// the rows scanned by sgpu_frames_scan_duplex_streams, likewise; count entries
+/// at most.
 SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count);
 /// Measurement aid: while on, flush assembly counts the executor launches'
 /// compulsory bytes -- each distinct source symbol read once, each

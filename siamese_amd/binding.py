@@ -106,6 +106,24 @@ def bind_streams_abi(L):
     return L
 
 
+STREAM_PARTIAL_DUPLEX = 0x10000000
+
+
+def bind_duplex_streams_abi(L):
+    """Prototypes of the scan of duplex byte-stream rows
+    (sgpu_frames_scan_duplex_streams and sgpu_frames_recv_duplex_streams)."""
+    vp, u, sz = ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t
+    L.sgpu_frames_duplex_streams_bytes.restype = sz
+    L.sgpu_frames_duplex_streams_bytes.argtypes = [u, u, u, u]
+    L.sgpu_frames_duplex_streams_next.restype = sz
+    L.sgpu_frames_duplex_streams_next.argtypes = [u, u, u, u]
+    L.sgpu_frames_scan_duplex_streams.restype = ctypes.c_longlong
+    L.sgpu_frames_scan_duplex_streams.argtypes = [vp, sz, vp, vp, u, u, u, u, u, u, vp]
+    L.sgpu_frames_recv_duplex_streams.restype = ctypes.c_int
+    L.sgpu_frames_recv_duplex_streams.argtypes = [vp, u, vp, u, vp, u, u, u, u, u, vp, sz, u, vp, vp, vp, vp, vp]
+    return L
+
+
 def bind_relay_pack_abi(L):
     """Prototype of sgpu_decoder_pack_frames: a decoder's packets as wire
     frames packed several to a row, laid out on the device."""

@@ -265,6 +265,20 @@ bool be_duplex_dense_rows(const void* rows, uint64_t stride, const uint32_t* len
 bool be_stream_rows(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends, uint32_t count,
                     uint32_t maxFrames, uint32_t maxRecords, void* devStage, void* hostOut, void** packed,
                     void** landed);
+/// The scan of duplex byte-stream rows (ops.h duplex_streams_bytes): four
+/// launches on the gather stream -- k_ackstreamwalk's walk of row bytes
+/// [starts[k], ends[k]) with the row's records, slots and ack count into the
+/// scratch areas (duplex_streams_scratch_*), the row words into the output and
+/// the next words behind its dense part, then k_rowsum2, k_compact and k_slots
+/// as in be_duplex_dense_rows -- all into devStage
+/// (duplex_streams_stage_bytes(...), device memory, 16-byte aligned), then one
+/// copy of the first duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes)
+/// bytes to hostOut (pinned), without waiting.  starts and ends are
+/// be_stream_rows'; rows, stride and the marks are be_scan_rows'.
+bool be_duplex_stream_rows(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends,
+                           uint32_t count, uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes,
+                           uint32_t maxRecords, uint32_t maxAcks, void* devStage, void* hostOut, void** packed,
+                           void** landed);
 /// Block until the device has passed `mark`, then recycle it; false on a
 /// device fault.
 bool be_mark_sync(void* mark);
@@ -272,11 +286,13 @@ bool be_mark_sync(void* mark);
 /// Device-time accounting: every executor/solve launch is bracketed with
 /// events; these return the accumulated milliseconds since the last reset.
 /// Kernel classes of the per-launch device timing.
-/// (kBeScan, kBeWalk, kBeAckWalk, kBeRowsum, kBeCompact, kBeRowsum2, kBeSlots and kBeStreamWalk are bracketed on
+/// (kBeScan, kBeWalk, kBeAckWalk, kBeRowsum, kBeCompact, kBeRowsum2, kBeSlots, kBeStreamWalk and kBeAckStreamWalk
+/// are bracketed on
 /// the gather stream: be_sync waits for a bracket of those classes still in flight before it folds
 /// it in; the dense scan's walk is counted as kBeWalk, the duplex dense scan's as kBeAckWalk and
 /// its k_compact as kBeCompact; the stream scan's walk has its own class, its k_rowsum and k_compact are
-/// counted as kBeRowsum and kBeCompact)
+/// counted as kBeRowsum and kBeCompact; the duplex stream scan's walk has its own class too, its k_rowsum2,
+/// k_compact and k_slots are counted as kBeRowsum2, kBeCompact and kBeSlots)
 enum BeKernel
 {
     kBeIngest,
@@ -299,6 +315,7 @@ enum BeKernel
     kBeRowsum2,
     kBeSlots,
     kBeStreamWalk,
+    kBeAckStreamWalk,
     kBeKernelKinds
 };
 void be_timing_enable(bool on);

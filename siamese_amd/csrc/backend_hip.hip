@@ -36,6 +36,8 @@
 //   k_ackwalkd, k_rowsum2, k_slots  k_ackwalk's records (through k_compact) and
 //                  used slots of all rows back to back: the walk into device
 //                  scratch, one prefix sum over both counts, then placed copies
+//   k_ackstreamwalk  k_ackwalkd for rows that are byte streams: bytes [start,
+//                  end), a cut-off last frame reported as partial, a next word
 //                  (header fields, a recovery packet's head and tail; opt-in)
 //
 // GF(256) multiply by a wave-uniform constant uses three v_perm_b32 byte
@@ -5212,16 +5214,39 @@ __global__ __launch_bounds__(kStreamWalkThreads) void k_streamwalk(uint64_t rows
 // row's slots from slot0 on (a used slot is written whole, zeros to its end),
 // *acksOut = the ack frames accepted and the row word n | flags is returned.
 // Records past the n-th and slots past the last used one are not written here.
-__device__ __forceinline__ uint32_t ackwalk_row(uint64_t row, uint64_t stride, uint64_t end, uint32_t maxFrames,
-                                                uint32_t ackSlots, uint32_t ackBytes, uint64_t rec, uint64_t slot0,
-                                                uint32_t* acksOut)
+//
+// kStream (k_ackstreamwalk; frames.h ack_stream_walk is the statement): the row
+// is a byte stream, walked over [start, end), and *nextOut = where its next scan
+// starts.  The cursor starts at `start`, so the first word's mask drops the
+// bytes before it as it drops those from `end` on in the last: stale bytes on
+// either side never reach a decision.  A frame that the left = end - at bytes
+// do not hold whole is classified from its header bytes below end alone (have =
+// left - h of them): the 16 bytes recombined at the cursor may hold stale bytes
+// behind end, or zeros where the word behind the row's last was not loaded, and
+// neither is looked at.  Without kStream, start and nextOut are unused and the
+// code is what k_ackwalk and k_ackwalkd have always run.
+template <bool kStream>
+__device__ __forceinline__ uint32_t ackwalk_row(uint64_t row, uint64_t stride, uint64_t start, uint64_t end,
+                                                uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes,
+                                                uint64_t rec, uint64_t slot0, uint32_t* acksOut, uint64_t* nextOut)
 {
     uint32_t n = 0, acks = 0, flags = 0;
-    if (end > stride) {
-        flags = kPackedMalformed;
-        end = 0;
-    }
     uint64_t at = 0;
+    uint64_t stop = end;   // (kStream: where the next scan starts; `end` when only zero bytes are left)
+    if constexpr (kStream) {
+        if (start > end || end > stride) {
+            flags = kPackedMalformed;
+            stop = start < stride ? start : stride;
+            end = 0;
+        } else {
+            at = start;
+        }
+    } else {
+        if (end > stride) {
+            flags = kPackedMalformed;
+            end = 0;
+        }
+    }
     while (at < end) {
         const uint64_t wa = at & ~(uint64_t)15;
         const uint4 A = ld16(row + wa);
@@ -5239,6 +5264,7 @@ __device__ __forceinline__ uint32_t ackwalk_row(uint64_t row, uint64_t stride, u
         at = wa + s;
         if (n == maxFrames) {
             flags |= kPackedMore;
+            stop = at;
             break;
         }
         // row bytes [at, at + 16), zero where the next word is not loaded
@@ -5255,6 +5281,27 @@ __device__ __forceinline__ uint32_t ackwalk_row(uint64_t row, uint64_t stride, u
         uint32_t L = 0;
         const int hp = parse_prefix((uint32_t)w0, left < 4 ? (uint32_t)left : 4u, &L);
         bool ok = hp >= 1 && L >= 1 && (uint64_t)hp + L <= left;
+        if constexpr (kStream) {
+            if (!ok) {   // not whole: partial, unless what is there can never become a valid frame
+                bool never = hp >= 1 && L < 1;
+                if (hp >= 1 && L >= 1) {
+                    const uint32_t h = (uint32_t)hp;
+                    const uint64_t have = left - h;   // header bytes behind the prefix that lie below end
+                    const uint64_t x = (w0 >> (8u * h)) | (w1 << (64u - 8u * h));
+                    const uint32_t type = (uint32_t)x & 0xffu;
+                    const uint32_t inner = type == 0 ? 7u : 4u;
+                    const uint32_t num = type == 0 ? (uint32_t)(x >> 32) & 0xffffffu : 0u;
+                    never = (uint64_t)h + L > stride;
+                    if (have >= 1)
+                        never = never || type > 2 || L <= inner;
+                    if (have >= 7)
+                        never = never || num > 0x3fffffu;
+                }
+                flags |= never ? kPackedMalformed : kStreamPartialDuplex;
+                stop = at;
+                break;
+            }
+        }
         uint4 r0 = make_uint4(0, 0, 0, 0), r1 = make_uint4(0, 0, 0, 0);
         uint32_t total = 0;
         if (ok) {
@@ -5337,6 +5384,7 @@ __device__ __forceinline__ uint32_t ackwalk_row(uint64_t row, uint64_t stride, u
         }
         if (!ok) {
             flags |= kPackedMalformed;
+            stop = at;
             break;
         }
         st16(rec + (uint64_t)n * 32, r0);
@@ -5344,6 +5392,8 @@ __device__ __forceinline__ uint32_t ackwalk_row(uint64_t row, uint64_t stride, u
         ++n;
         at += total;
     }
+    if constexpr (kStream)
+        *nextOut = stop;
     *acksOut = acks;
     return n | flags;
 }
@@ -5359,8 +5409,8 @@ __global__ __launch_bounds__(kAckWalkThreads) void k_ackwalk(uint64_t rows, uint
     const uint64_t rec = out + k * maxFrames * 32;
     const uint64_t slot0 = slots + k * ackSlots * ackBytes;
     uint32_t acks = 0;
-    const uint32_t word = ackwalk_row(rows + k * stride, stride, lens ? lens[k] : stride, maxFrames, ackSlots,
-                                      ackBytes, rec, slot0, &acks);
+    const uint32_t word = ackwalk_row<false>(rows + k * stride, stride, 0, lens ? lens[k] : stride, maxFrames,
+                                             ackSlots, ackBytes, rec, slot0, &acks, nullptr);
     for (uint32_t j = word & kPackedCountMask; j < maxFrames; ++j) {   // every record is written by every scan
         st16(rec + (uint64_t)j * 32, make_uint4(0, 0, 0, 0));
         st16(rec + (uint64_t)j * 32 + 16, make_uint4(0, 0, 0, 0));
@@ -5401,9 +5451,37 @@ __global__ __launch_bounds__(kAckWalkdThreads) void k_ackwalkd(uint64_t rows, ui
         return;
     uint32_t acks = 0;
     *reinterpret_cast<GMEM uint32_t*>(words + k * 4) =
-        ackwalk_row(rows + k * stride, stride, lens ? lens[k] : stride, maxFrames, ackSlots, ackBytes,
-                    scratchRecs + k * maxFrames * 32, scratchSlots + k * ackSlots * ackBytes, &acks);
+        ackwalk_row<false>(rows + k * stride, stride, 0, lens ? lens[k] : stride, maxFrames, ackSlots, ackBytes,
+                           scratchRecs + k * maxFrames * 32, scratchSlots + k * ackSlots * ackBytes, &acks, nullptr);
     *reinterpret_cast<GMEM uint32_t*>(scratchCounts + k * 4) = acks < ackSlots ? acks : ackSlots;
+}
+
+// k_ackstreamwalk (ops.h duplex_streams_bytes): k_ackwalkd for rows that are
+// byte streams -- the same lane per row and the same scratch areas, the walk in
+// its stream mode over row bytes [starts[k], ends[k]), and the row's next word
+// behind the output's dense part.  The row word may carry kStreamPartialDuplex;
+// k_rowsum2 masks the word with kPackedCountMask before it sums, so the flag
+// rides along as the others do, and k_compact and k_slots read only the tables:
+// all three run unchanged behind this walk.  No LDS, no atomics.
+__global__ __launch_bounds__(kAckStreamWalkThreads) void k_ackstreamwalk(
+    uint64_t rows, uint64_t stride, const uint32_t* __restrict__ starts, const uint32_t* __restrict__ ends,
+    uint32_t count, uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes, uint64_t scratchRecs,
+    uint64_t scratchSlots, uint64_t scratchCounts, uint64_t words, uint64_t nexts)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kAckStreamWalkThreads + threadIdx.x;
+    if (k >= count)
+        return;
+    uint32_t acks = 0;
+    uint64_t next = 0;
+    *reinterpret_cast<GMEM uint32_t*>(words + k * 4) = ackwalk_row<true>(
+        rows + k * stride, stride, starts ? starts[k] : 0, ends ? ends[k] : stride, maxFrames, ackSlots, ackBytes,
+        scratchRecs + k * maxFrames * 32, scratchSlots + k * ackSlots * ackBytes, &acks, &next);
+    *reinterpret_cast<GMEM uint32_t*>(scratchCounts + k * 4) = acks < ackSlots ? acks : ackSlots;
+    *reinterpret_cast<GMEM uint32_t*>(nexts + k * 4) = next < 0xffffffffull ? (uint32_t)next : 0xffffffffu;
+    // the zeros between the next words and the next 16-byte boundary: every byte is written by every scan
+    if (k + 1 == count)
+        for (uint64_t j = count; j < (((uint64_t)count + 3) & ~(uint64_t)3); ++j)
+            *reinterpret_cast<GMEM uint32_t*>(nexts + j * 4) = 0;
 }
 
 // wave_incl_sum on two 32-bit sums at once, the records' in the low half and
@@ -5682,7 +5760,7 @@ void harvest_timing(bool all)
         // (a synchronised codec stream says nothing about the gather stream)
         if (all && (ev.kind == kBeScan || ev.kind == kBeWalk || ev.kind == kBeAckWalk || ev.kind == kBeRowsum ||
                     ev.kind == kBeCompact || ev.kind == kBeRowsum2 || ev.kind == kBeSlots ||
-                    ev.kind == kBeStreamWalk))
+                    ev.kind == kBeStreamWalk || ev.kind == kBeAckStreamWalk))
             (void)hipEventSynchronize(ev.b);
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.a, ev.b);
@@ -6790,6 +6868,63 @@ bool be_duplex_dense_rows(const void* rows, uint64_t stride, const uint32_t* len
                            maxAcks);
     }
     if (hipMemcpyAsync(hostOut, devStage, (size_t)duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes),
+                       hipMemcpyDeviceToHost, g_gatherStream) != hipSuccess ||
+        hipEventRecord(l, g_gatherStream) != hipSuccess) {
+        be_mark_release(l);
+        return false;
+    }
+    *landed = l;
+    return true;
+}
+
+bool be_duplex_stream_rows(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends,
+                           uint32_t count, uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes,
+                           uint32_t maxRecords, uint32_t maxAcks, void* devStage, void* hostOut, void** packed,
+                           void** landed)
+{
+    bind_device();
+    *packed = *landed = nullptr;
+    hipEvent_t p = take_mark(), l = take_mark();
+    if (!p || !l) {
+        be_mark_release(p);
+        be_mark_release(l);
+        return false;
+    }
+    const uint64_t out = (uint64_t)(uintptr_t)devStage;
+    const uint64_t recs = out + duplex_streams_scratch_records(count, maxRecords, maxAcks, ackBytes);
+    const uint64_t slots = out + duplex_streams_scratch_slots(count, maxFrames, maxRecords, maxAcks, ackBytes);
+    const uint64_t counts =
+        out + duplex_streams_scratch_counts(count, maxFrames, ackSlots, maxRecords, maxAcks, ackBytes);
+    {
+        Timed t(kBeAckStreamWalk, g_gatherStream);
+        hipLaunchKernelGGL(k_ackstreamwalk, dim3((count + kAckStreamWalkThreads - 1) / kAckStreamWalkThreads),
+                           dim3(kAckStreamWalkThreads), 0, g_gatherStream, (uint64_t)(uintptr_t)rows, stride, starts,
+                           ends, count, maxFrames, ackSlots, ackBytes, recs, slots, counts, out + 16,
+                           out + duplex_streams_next_offset(count, maxRecords, maxAcks, ackBytes));
+    }
+    // (the rows have been read: what follows works on the staging area alone)
+    if (hipEventRecord(p, g_gatherStream) != hipSuccess)
+        return false;
+    *packed = p;
+    {
+        Timed t(kBeRowsum2, g_gatherStream);
+        hipLaunchKernelGGL(k_rowsum2, dim3(1), dim3(kRowsum2Threads), 0, g_gatherStream, out, counts, count,
+                           maxFrames, ackSlots, maxRecords, maxAcks);
+    }
+    {
+        Timed t(kBeCompact, g_gatherStream);
+        const uint64_t lanes = 2 * (uint64_t)maxRecords;
+        hipLaunchKernelGGL(k_compact, dim3((uint32_t)((lanes + kCompactThreads - 1) / kCompactThreads)),
+                           dim3(kCompactThreads), 0, g_gatherStream, out, recs, count, maxFrames, maxRecords);
+    }
+    {
+        Timed t(kBeSlots, g_gatherStream);
+        const uint64_t lanes = (uint64_t)maxAcks * (ackBytes >> 4);
+        hipLaunchKernelGGL(k_slots, dim3((uint32_t)((lanes + kSlotsThreads - 1) / kSlotsThreads)),
+                           dim3(kSlotsThreads), 0, g_gatherStream, out, slots, count, ackSlots, ackBytes, maxRecords,
+                           maxAcks);
+    }
+    if (hipMemcpyAsync(hostOut, devStage, (size_t)duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes),
                        hipMemcpyDeviceToHost, g_gatherStream) != hipSuccess ||
         hipEventRecord(l, g_gatherStream) != hipSuccess) {
         be_mark_release(l);

@@ -1347,13 +1347,14 @@ SIAMESE_EXPORT long long sgpu_frames_scan_duplex_dense(const void* deviceRows, s
                                                                 count ? maxAcks : 0, pinnedOut);
 }
 
-SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* decoders, unsigned decoderCount,
-                                                           const SgpuEncoder* encoders, unsigned encoderCount,
-                                                           const void* heads, unsigned maxFrames, unsigned ackSlots,
-                                                           unsigned ackBytes, unsigned maxRecords, unsigned maxAcks,
-                                                           const void* deviceRows, size_t stride, unsigned count,
-                                                           SiameseResult* results, unsigned* nextExpectedOut,
-                                                           unsigned* rowsOut, unsigned* acceptedOut)
+namespace {
+// sgpu_frames_recv_duplex_dense and, with the next words behind the dense part (streams) and consumedOut,
+// sgpu_frames_recv_duplex_streams
+SiameseResult recv_duplex_dense_rows(const SgpuDecoder* decoders, unsigned decoderCount, const SgpuEncoder* encoders,
+                                     unsigned encoderCount, const void* heads, unsigned maxFrames, unsigned ackSlots,
+                                     unsigned ackBytes, unsigned maxRecords, unsigned maxAcks, const void* deviceRows,
+                                     size_t stride, unsigned count, SiameseResult* results, unsigned* nextExpectedOut,
+                                     bool streams, unsigned* consumedOut, unsigned* rowsOut, unsigned* acceptedOut)
 {
     if (rowsOut)
         *rowsOut = 0;
@@ -1362,7 +1363,8 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* de
     *acceptedOut = 0;
     if (!rowsOut || !rows_ok(deviceRows, stride, count) || (!heads && count > 0) || (!decoders && decoderCount) ||
         (!encoders && encoderCount) || ((uintptr_t)heads & 3) || !duplex_ok(maxFrames, ackSlots, ackBytes) ||
-        (count > 0 && !duplex_dense_ok(count, maxFrames, ackSlots, ackBytes, maxRecords, maxAcks)))
+        (count > 0 && !duplex_dense_ok(count, maxFrames, ackSlots, ackBytes, maxRecords, maxAcks)) ||
+        (streams && !consumedOut && count > 0))
         return Siamese_InvalidInput;
     if (count == 0)
         return Siamese_Success;
@@ -1376,6 +1378,8 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* de
     const uint8_t* recs = base + (size_t)dense_records_offset(count);
     const uint8_t* astarts = base + (size_t)duplex_dense_acks_offset(count, maxRecords);
     const uint8_t* slots = base + (size_t)duplex_dense_slots_offset(count, maxRecords);
+    const uint8_t* nextWords =
+        streams ? base + (size_t)duplex_streams_next_offset(count, maxRecords, maxAcks, ackBytes) : nullptr;
     uint32_t info[4];
     std::memcpy(info, base, sizeof(info));
     const uint32_t W = info[1], c = info[2], WA = info[3];
@@ -1417,6 +1421,21 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* de
             n = 0;
             malformed = true;
         }
+        uint32_t resume = 0;
+        if (nextWords) {
+            // where the row's next scan starts: within the row, and not before the end of its last record
+            std::memcpy(&resume, nextWords + (size_t)k * 4, 4);
+            uint64_t least = 0;
+            if (n > 0) {
+                PackedHead h;
+                std::memcpy(&h, recs + ((size_t)at + n - 1) * sizeof(h), sizeof(h));
+                least = (uint64_t)h.offset + h.headerBytes + h.dataBytes;
+            }
+            if (resume > stride || resume < least) {
+                forged = true;
+                break;
+            }
+        }
         unsigned acks = 0;   // ack records met in this row
         for (unsigned j = 0; j < n; ++j) {
             PackedHead h;
@@ -1432,6 +1451,8 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* de
         }
         if (malformed && status == Siamese_Success)   // (the frame the walk stopped at has no slot here)
             status = Siamese_InvalidInput;
+        if (nextWords)
+            consumedOut[k] = resume;
         at = next;
         aat = anext;
     }
@@ -1440,6 +1461,77 @@ SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* de
     *rowsOut = k;   // c, unless a table stopped the routing before it
     *acceptedOut = accepted;
     return forged ? Siamese_InvalidInput : status;
+}
+} // namespace
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_dense(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                           const SgpuEncoder* encoders, unsigned encoderCount,
+                                                           const void* heads, unsigned maxFrames, unsigned ackSlots,
+                                                           unsigned ackBytes, unsigned maxRecords, unsigned maxAcks,
+                                                           const void* deviceRows, size_t stride, unsigned count,
+                                                           SiameseResult* results, unsigned* nextExpectedOut,
+                                                           unsigned* rowsOut, unsigned* acceptedOut)
+{
+    return recv_duplex_dense_rows(decoders, decoderCount, encoders, encoderCount, heads, maxFrames, ackSlots,
+                                  ackBytes, maxRecords, maxAcks, deviceRows, stride, count, results, nextExpectedOut,
+                                  false, nullptr, rowsOut, acceptedOut);
+}
+
+static_assert(SGPU_STREAM_PARTIAL_DUPLEX == kStreamPartialDuplex &&
+                  !(SGPU_STREAM_PARTIAL_DUPLEX &
+                    (kPackedCountMask | kPackedMore | kPackedMalformed | kPackedAcksDropped)),
+              "the duplex stream scan's row word");
+
+SIAMESE_EXPORT size_t sgpu_frames_duplex_streams_bytes(unsigned count, unsigned maxRecords, unsigned maxAcks,
+                                                       unsigned ackBytes)
+{
+    return sgpu_frames_duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes)
+               ? (size_t)duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes)
+               : 0;
+}
+
+SIAMESE_EXPORT size_t sgpu_frames_duplex_streams_next(unsigned count, unsigned maxRecords, unsigned maxAcks,
+                                                      unsigned ackBytes)
+{
+    return sgpu_frames_duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes)
+               ? (size_t)duplex_streams_next_offset(count, maxRecords, maxAcks, ackBytes)
+               : 0;
+}
+
+SIAMESE_EXPORT long long sgpu_frames_scan_duplex_streams(const void* deviceRows, size_t stride,
+                                                         const unsigned* deviceStarts, const unsigned* deviceEnds,
+                                                         unsigned count, unsigned maxFrames, unsigned ackSlots,
+                                                         unsigned ackBytes, unsigned maxRecords, unsigned maxAcks,
+                                                         void* pinnedOut)
+{
+    if (!g_batchReady || !rows_ok(deviceRows, stride, count) || ((uintptr_t)deviceStarts & 3) ||
+        ((uintptr_t)deviceEnds & 3) || ((uintptr_t)pinnedOut & 15) || (!pinnedOut && count > 0) ||
+        !duplex_ok(maxFrames, ackSlots, ackBytes) ||
+        duplex_bytes(count, maxFrames, ackSlots, ackBytes) > ((uint64_t)1 << 32))
+        return -1;
+    // (count == 0 admits no maxRecords >= maxFrames: its ticket is complete and nothing is written)
+    if (count > 0 && (!duplex_dense_ok(count, maxFrames, ackSlots, ackBytes, maxRecords, maxAcks) ||
+                      duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes) >= ((uint64_t)1 << 32)))
+        return -1;
+    return (long long)Engine::global()->duplex_stream_rows_async(deviceRows, stride, deviceStarts, deviceEnds, count,
+                                                                 maxFrames, ackSlots, ackBytes,
+                                                                 count ? maxRecords : 0, count ? maxAcks : 0,
+                                                                 pinnedOut);
+}
+
+SIAMESE_EXPORT SiameseResult sgpu_frames_recv_duplex_streams(const SgpuDecoder* decoders, unsigned decoderCount,
+                                                             const SgpuEncoder* encoders, unsigned encoderCount,
+                                                             const void* heads, unsigned maxFrames,
+                                                             unsigned ackSlots, unsigned ackBytes,
+                                                             unsigned maxRecords, unsigned maxAcks,
+                                                             const void* deviceRows, size_t stride, unsigned count,
+                                                             SiameseResult* results, unsigned* nextExpectedOut,
+                                                             unsigned* consumedOut, unsigned* rowsOut,
+                                                             unsigned* acceptedOut)
+{
+    return recv_duplex_dense_rows(decoders, decoderCount, encoders, encoderCount, heads, maxFrames, ackSlots,
+                                  ackBytes, maxRecords, maxAcks, deviceRows, stride, count, results, nextExpectedOut,
+                                  true, consumedOut, rowsOut, acceptedOut);
 }
 
 SIAMESE_EXPORT long long sgpu_frames_send(unsigned count, const SgpuRecoveryPacket* packets, const unsigned* flows,
@@ -1491,7 +1583,7 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
 {
     const EngineStats s = Engine::global()->stats();
     const Engine* e = Engine::global();
-    const uint64_t v[43] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
+    const uint64_t v[44] = {s.flushes,    s.launches,    s.ops,        s.terms,    s.solves,
                             s.ingests,    s.uploadBytes, s.refOpBytes, s.outBytes, s.solveBytes,
                             s.assembleNs, s.waitNs,      s.completeNs, s.reclaimNs,
                             s.execLaunches, s.ldpcBytes, s.execUniqueBytes,
@@ -1503,8 +1595,9 @@ SIAMESE_EXPORT void sgpu_engine_stats_ex(uint64_t* out, unsigned count)
                             e->rows_shape(0), e->rows_shape(1), e->rows_shape(2), e->rows_shape(3),
                             e->rows_shape(4), be_exec_stage_cap(),
                             e->denses(),  s.gePivoted,   s.geSingular,
-                            e->duplex_denses(), e->solves_flagged(), e->solves_cut(), e->streams()};
-    for (unsigned k = 0; k < count && k < 43; ++k)
+                            e->duplex_denses(), e->solves_flagged(), e->solves_cut(), e->streams(),
+                            e->duplex_streams()};
+    for (unsigned k = 0; k < count && k < 44; ++k)
         out[k] = v[k];
 }
 

@@ -3169,7 +3169,8 @@ int64_t Engine::gather_async_framed(unsigned count, const void* const* srcs, con
 // and duplex_rows_async (ackSlots != 0: k_ackwalk) and dense_rows_async
 // (maxRecords != 0: k_walkd, k_rowsum and k_compact) and duplex_dense_rows_async (maxRecords != 0 and
 // ackSlots != 0: k_ackwalkd, k_rowsum2, k_compact and k_slots) and stream_rows_async (streams: k_streamwalk,
-// k_rowsum and k_compact, with lens as the rows' ends)
+// k_rowsum and k_compact, with lens as the rows' ends) and duplex_stream_rows_async (streams and ackSlots != 0:
+// k_ackstreamwalk, k_rowsum2, k_compact and k_slots)
 int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* lens, unsigned count,
                            unsigned maxFrames, void* pinnedOut, unsigned ackSlots, unsigned ackBytes,
                            unsigned maxRecords, unsigned maxAcks, bool streams, const uint32_t* starts)
@@ -3186,7 +3187,10 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     // the records take the slot's packing area (the dense scans' scratch areas behind their output); a scan
     // uploads no descriptors
     const bool duplexDense = maxRecords && ackSlots;
-    const size_t total = streams     ? (size_t)streams_stage_bytes(count, maxFrames, maxRecords)
+    const bool duplexStreams = streams && ackSlots;
+    const size_t total = duplexStreams ? (size_t)duplex_streams_stage_bytes(count, maxFrames, ackSlots, maxRecords,
+                                                                            maxAcks, ackBytes)
+                         : streams   ? (size_t)streams_stage_bytes(count, maxFrames, maxRecords)
                          : duplexDense ? (size_t)duplex_dense_stage_bytes(count, maxFrames, ackSlots, maxRecords,
                                                                           maxAcks, ackBytes)
                          : maxRecords ? (size_t)dense_stage_bytes(count, maxFrames, maxRecords)
@@ -3205,7 +3209,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
     if (!g.stage)
         return -1;
     void* packed = nullptr;
-    if (!(streams     ? be_stream_rows(rows, stride, starts, lens, count, maxFrames, maxRecords, g.stage, pinnedOut,
+    if (!(duplexStreams ? be_duplex_stream_rows(rows, stride, starts, lens, count, maxFrames, ackSlots, ackBytes,
+                                                maxRecords, maxAcks, g.stage, pinnedOut, &packed, &g.landed)
+          : streams   ? be_stream_rows(rows, stride, starts, lens, count, maxFrames, maxRecords, g.stage, pinnedOut,
                                        &packed, &g.landed)
           : duplexDense ? be_duplex_dense_rows(rows, stride, lens, count, maxFrames, ackSlots, ackBytes, maxRecords,
                                                maxAcks, g.stage, pinnedOut, &packed, &g.landed)
@@ -3219,7 +3225,9 @@ int64_t Engine::rows_async(const void* rows, uint64_t stride, const uint32_t* le
         return -1;
     }
     g.ticket = ticket;
-    if (streams)
+    if (duplexStreams)
+        duplexStreams_.fetch_add(count, std::memory_order_relaxed);
+    else if (streams)
         streams_.fetch_add(count, std::memory_order_relaxed);
     else if (duplexDense)
         duplexDenses_.fetch_add(count, std::memory_order_relaxed);

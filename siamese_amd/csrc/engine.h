@@ -825,6 +825,19 @@ public:
     {
         return rows_async(rows, stride, ends, count, maxFrames, pinnedOut, 0, 0, maxRecords, 0, true, starts);
     }
+    /// stream_rows_async for the rows of a bidirectional flow: acknowledgement
+    /// frames accepted as in duplex_dense_rows_async, the duplex dense output and
+    /// behind it one next word per row, duplex_streams_bytes(count, maxRecords,
+    /// maxAcks, ackBytes) in all, into pinnedOut (k_ackstreamwalk, k_rowsum2,
+    /// k_compact and k_slots, sgpu_frames_scan_duplex_streams).  The same gather
+    /// slots, tickets and staging.
+    int64_t duplex_stream_rows_async(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends,
+                                     unsigned count, unsigned maxFrames, unsigned ackSlots, unsigned ackBytes,
+                                     unsigned maxRecords, unsigned maxAcks, void* pinnedOut)
+    {
+        return rows_async(rows, stride, ends, count, maxFrames, pinnedOut, ackSlots, ackBytes, maxRecords, maxAcks,
+                          true, starts);
+    }
     /// Wait until gather `ticket` and every earlier one have landed.
     bool gather_wait(int64_t ticket);
     /// Host -> device copy on the staging stream, issued now; every later
@@ -1031,6 +1044,8 @@ private:
     std::atomic<uint64_t> solvesCut_{0};
     // rows scanned by the stream scan, counted as walks_ ([42]); here for the same reason
     std::atomic<uint64_t> streams_{0};
+    // rows scanned by the duplex stream scan, counted as walks_ ([43]); here for the same reason
+    std::atomic<uint64_t> duplexStreams_{0};
 
 public:
     uint64_t rows_shape(unsigned k) const { return rowsShape_[k].load(std::memory_order_relaxed); }
@@ -1040,6 +1055,7 @@ public:
     uint64_t denses() const { return denses_.load(std::memory_order_relaxed); }
     uint64_t duplex_denses() const { return duplexDenses_.load(std::memory_order_relaxed); }
     uint64_t streams() const { return streams_.load(std::memory_order_relaxed); }
+    uint64_t duplex_streams() const { return duplexStreams_.load(std::memory_order_relaxed); }
     uint64_t solves_flagged() const { return solvesFlagged_.load(std::memory_order_relaxed); }
     uint64_t solves_cut() const { return solvesCut_.load(std::memory_order_relaxed); }
     void count_solve_outcome(bool flagged, bool cut)

@@ -487,6 +487,112 @@ inline uint32_t ack_walk(const uint8_t* row, uint64_t stride, const uint32_t* le
     return n | flags;
 }
 
+/// What k_ackstreamwalk computes for one row of a duplex byte stream (ops.h
+/// kStreamPartialDuplex, sgpu_frames_scan_duplex_streams /
+/// sgpu_frames_recv_duplex_streams): ack_walk and stream_walk as one function.
+/// row[0, stride) in host memory, out = the row's maxFrames records, slots = its
+/// ackSlots message slots of ackBytes bytes, *next = the row offset from which
+/// the row's next scan must start.  start > end or end > stride is a malformed
+/// row without records or acks and *next = min(start, stride).  Otherwise
+/// row[start, end) is walked as ack_walk walks row[0, end) -- types 0, 1 and 2,
+/// the row's a-th ack of this scan with packetNum = a, slot a and the truncated
+/// rule -- with stream_walk's outcomes: a frame at `at` that the left = end - at
+/// bytes do not hold whole ends the walk with kStreamPartialDuplex, or with
+/// kPackedMalformed when something present can never become valid (w + L >
+/// stride, a type byte that is present and above kFrameAck, a type byte that is
+/// present with L <= the type's inner header, an original whose three PacketNum
+/// bytes are present and exceed SIAMESE_PACKET_NUM_MAX).  A partial ack writes
+/// no slot, gets no record and is not counted.  *next is stream_walk's.  The word
+/// may carry kPackedAcksDropped beside any one stop flag.  Every record and
+/// every slot byte is written.  Returns the row word.
+inline uint32_t ack_stream_walk(const uint8_t* row, uint64_t stride, uint64_t start, uint64_t end, uint32_t maxFrames,
+                                uint32_t ackSlots, uint32_t ackBytes, PackedHead* out, uint8_t* slots, uint32_t* next)
+{
+    std::memset(out, 0, (size_t)maxFrames * sizeof(*out));
+    std::memset(slots, 0, (size_t)ackSlots * ackBytes);
+    if (start > end || end > stride) {
+        *next = (uint32_t)(start < stride ? start : stride);
+        return kPackedMalformed;
+    }
+    uint64_t at = start;
+    uint32_t n = 0, acks = 0, flags = 0;
+    while (at < end) {
+        if (row[at] == 0) {
+            ++at;
+            continue;
+        }
+        *next = (uint32_t)at;
+        if (n == maxFrames)
+            return n | flags | kPackedMore;
+        const uint64_t left = end - at;
+        unsigned length = 0;
+        const int h = read_length_prefix(row + at, left < 4 ? (unsigned)left : 4u, &length);
+        if (h < 1)
+            return n | flags | kStreamPartialDuplex;   // (the prefix itself is cut off)
+        if (length < 1)
+            return n | flags | kPackedMalformed;
+        const uint8_t* f = row + at + h;   // type, flow, PacketNum: the first left - h of them are there
+        if ((uint64_t)h + length > left) {
+            const uint64_t have = left - h;
+            bool never = (uint64_t)h + length > stride;
+            if (have >= 1) {
+                const unsigned inner = f[0] == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+                never = never || f[0] > kFrameAck || length <= inner;
+                if (f[0] == kFrameOriginal && have >= kFrameOriginalInner)
+                    never = never || (f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16)) > SIAMESE_PACKET_NUM_MAX;
+            }
+            return n | flags | (never ? kPackedMalformed : kStreamPartialDuplex);
+        }
+        PackedHead r;
+        std::memset(&r, 0, sizeof(r));
+        r.offset = (uint32_t)at;
+        r.status = kRowOk;
+        r.type = f[0];
+        const unsigned inner = r.type == kFrameOriginal ? kFrameOriginalInner : kFrameRecoveryInner;
+        if (r.type > kFrameAck || length <= inner)
+            return n | flags | kPackedMalformed;
+        r.headerBytes = (uint8_t)(h + inner);
+        r.flow = f[1] | ((uint32_t)f[2] << 8) | ((uint32_t)f[3] << 16);
+        r.dataBytes = length - inner;
+        if (r.type == kFrameAck) {
+            r.packetNum = acks;
+            if (acks < ackSlots)
+                std::memcpy(slots + (size_t)acks * ackBytes, row + at + r.headerBytes,
+                            r.dataBytes < ackBytes ? r.dataBytes : ackBytes);
+            if (acks >= ackSlots || r.dataBytes > ackBytes) {
+                r.status = kRowTruncated;
+                flags |= kPackedAcksDropped;
+            }
+            ++acks;
+        } else {
+            r.packetNum = r.type == kFrameOriginal ? f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) : 0;
+            r.tailBytes = r.type == kFrameRecovery ? (uint8_t)(r.dataBytes < 8 ? r.dataBytes : 8) : 0;
+            if (!packed_head_valid(r, end))
+                return n | flags | kPackedMalformed;
+            if (r.type == kFrameRecovery) {
+                const uint8_t* data = row + at + r.headerBytes;
+                std::memcpy(r.head, data, r.dataBytes < 4 ? r.dataBytes : 4);
+                std::memcpy(r.tail + 8 - r.tailBytes, data + r.dataBytes - r.tailBytes, r.tailBytes);
+            }
+        }
+        out[n++] = r;
+        at += (uint64_t)h + length;
+    }
+    *next = end < 0xffffffffu ? (uint32_t)end : 0xffffffffu;   // (end = stride = 4 GiB: the row's last byte, a zero)
+    return n | flags;
+}
+
+/// The next words behind a duplex stream scan's dense part (ops.h
+/// duplex_streams_bytes): out = duplex_streams_bytes(...) bytes whose first
+/// duplex_dense_bytes(...) duplex_dense_compact has written.
+inline void duplex_streams_put_next(const uint32_t* next, uint32_t count, uint32_t maxRecords, uint32_t maxAcks,
+                                    uint32_t ackBytes, uint8_t* out)
+{
+    const size_t at = (size_t)duplex_streams_next_offset(count, maxRecords, maxAcks, ackBytes);
+    std::memset(out + at, 0, (size_t)duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes) - at);
+    std::memcpy(out + at, next, (size_t)count * 4);
+}
+
 /// What k_rowsum2, k_compact and k_slots compute from ack_walk's output (ops.h
 /// duplex_dense_bytes states the layout, sgpu_frames_scan_duplex_dense /
 /// sgpu_frames_recv_duplex_dense use it): words = the count row words, rowRecs =

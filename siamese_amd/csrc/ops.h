@@ -815,6 +815,56 @@ constexpr uint64_t streams_stage_bytes(uint64_t count, uint64_t maxFrames, uint6
     return streams_scratch_offset(count, maxRecords) + count * maxFrames * sizeof(PackedHead);
 }
 
+/// Duplex byte-stream rows (k_ackstreamwalk, k_rowsum2, k_compact and k_slots,
+/// sgpu_frames_scan_duplex_streams): the stream rows above with acknowledgement
+/// frames accepted.  The output is the duplex dense layout (duplex_dense_bytes)
+/// and behind it
+///   count next words | zeros to the next 16-byte boundary
+/// where row word k is k_ackwalk's and may also carry kStreamPartialDuplex, and
+/// next_k is stream_walk's (frames.h ack_stream_walk states the walk).  The
+/// partial flag has a bit of its own here: kStreamPartial is kPackedAcksDropped's
+/// bit, and a duplex stream row can have dropped an ack and stop at a partial
+/// frame in one scan.
+///
+/// On the device the walk takes one lane per row, kAckStreamWalkThreads rows per
+/// workgroup (k_ackwalkd's scheme: DESIGN.md 2.2 has the measurement that ruled
+/// out a second wave-per-row walk); its scratch areas lie behind the output in
+/// the duplex dense scan's order.  Every offset below is a multiple of 16.
+constexpr uint32_t kStreamPartialDuplex = 0x10000000u;
+constexpr uint32_t kAckStreamWalkThreads = 256;
+constexpr uint64_t duplex_streams_next_offset(uint64_t count, uint64_t maxRecords, uint64_t maxAcks,
+                                              uint64_t ackBytes)
+{
+    return duplex_dense_bytes(count, maxRecords, maxAcks, ackBytes);
+}
+constexpr uint64_t duplex_streams_bytes(uint64_t count, uint64_t maxRecords, uint64_t maxAcks, uint64_t ackBytes)
+{
+    return duplex_streams_next_offset(count, maxRecords, maxAcks, ackBytes) + ((count * 4 + 15) & ~(uint64_t)15);
+}
+constexpr uint64_t duplex_streams_scratch_records(uint64_t count, uint64_t maxRecords, uint64_t maxAcks,
+                                                  uint64_t ackBytes)
+{
+    return duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes);
+}
+constexpr uint64_t duplex_streams_scratch_slots(uint64_t count, uint64_t maxFrames, uint64_t maxRecords,
+                                                uint64_t maxAcks, uint64_t ackBytes)
+{
+    return duplex_streams_scratch_records(count, maxRecords, maxAcks, ackBytes) +
+           count * maxFrames * sizeof(PackedHead);
+}
+constexpr uint64_t duplex_streams_scratch_counts(uint64_t count, uint64_t maxFrames, uint64_t ackSlots,
+                                                 uint64_t maxRecords, uint64_t maxAcks, uint64_t ackBytes)
+{
+    return duplex_streams_scratch_slots(count, maxFrames, maxRecords, maxAcks, ackBytes) +
+           count * ackSlots * ackBytes;
+}
+constexpr uint64_t duplex_streams_stage_bytes(uint64_t count, uint64_t maxFrames, uint64_t ackSlots,
+                                              uint64_t maxRecords, uint64_t maxAcks, uint64_t ackBytes)
+{
+    return duplex_streams_scratch_counts(count, maxFrames, ackSlots, maxRecords, maxAcks, ackBytes) +
+           ((count * 4 + 15) & ~(uint64_t)15);
+}
+
 constexpr unsigned kTileBytes = 1024;       // solve tiles: 64 lanes x 16 bytes
 constexpr unsigned kIngestChunkBytes = 8192;   // k_ingest: bytes per wave (8 x 1 KiB tiles)
 /// Solves with more rows than this stage 256-byte tiles (16 lanes x 16 bytes

@@ -839,6 +839,30 @@ bool be_stream_rows(const void* rows, uint64_t stride, const uint32_t* starts, c
     return true;
 }
 
+// k_ackstreamwalk, k_rowsum2, k_compact and k_slots (ops.h duplex_streams_bytes):
+// frames.h ack_stream_walk per row into the scratch areas, then frames.h
+// duplex_dense_compact and the next words.
+bool be_duplex_stream_rows(const void* rows, uint64_t stride, const uint32_t* starts, const uint32_t* ends,
+                           uint32_t count, uint32_t maxFrames, uint32_t ackSlots, uint32_t ackBytes,
+                           uint32_t maxRecords, uint32_t maxAcks, void* devStage, void* hostOut, void** packed,
+                           void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    uint8_t* out = static_cast<uint8_t*>(devStage);
+    PackedHead* recs =
+        reinterpret_cast<PackedHead*>(out + (size_t)duplex_streams_scratch_records(count, maxRecords, maxAcks, ackBytes));
+    uint8_t* slots = out + (size_t)duplex_streams_scratch_slots(count, maxFrames, maxRecords, maxAcks, ackBytes);
+    std::vector<uint32_t> words(count), next(count);
+    for (uint32_t k = 0; k < count; ++k)
+        words[k] = ack_stream_walk(static_cast<const uint8_t*>(rows) + (uint64_t)k * stride, stride,
+                                   starts ? starts[k] : 0, ends ? ends[k] : stride, maxFrames, ackSlots, ackBytes,
+                                   recs + (size_t)k * maxFrames, slots + (size_t)k * ackSlots * ackBytes, &next[k]);
+    duplex_dense_compact(words.data(), recs, slots, count, maxFrames, ackSlots, ackBytes, maxRecords, maxAcks, out);
+    duplex_streams_put_next(next.data(), count, maxRecords, maxAcks, ackBytes, out);
+    std::memcpy(hostOut, devStage, (size_t)duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes));
+    return true;
+}
+
 // HOSTSIM_FAIL_SYNC=N: the N-th be_sync (1-based) and every later one
 // report a device fault (tests of the sticky Disabled path).
 bool be_sync()

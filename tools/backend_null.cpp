@@ -189,6 +189,18 @@ bool be_stream_rows(const void*, uint64_t, const uint32_t*, const uint32_t*, uin
     return true;
 }
 
+bool be_duplex_stream_rows(const void*, uint64_t, const uint32_t*, const uint32_t*, uint32_t count, uint32_t,
+                           uint32_t, uint32_t ackBytes, uint32_t maxRecords, uint32_t maxAcks, void* devStage,
+                           void* hostOut, void** packed, void** landed)
+{
+    *packed = *landed = reinterpret_cast<void*>(1);
+    const size_t bytes = (size_t)duplex_streams_bytes(count, maxRecords, maxAcks, ackBytes);
+    std::memset(devStage, 0, bytes);
+    std::memcpy(static_cast<uint8_t*>(devStage) + 8, &count, 4);   // info {0, 0, c = count, 0}, every next word 0
+    std::memcpy(hostOut, devStage, bytes);
+    return true;
+}
+
 bool be_sync() { return true; }
 void* be_fence() { return reinterpret_cast<void*>(1); }
 bool be_fence_wait(void*, unsigned, bool) { return true; }
