@@ -285,6 +285,8 @@ SIAMESE_EXPORT void sgpu_host_free(void* p);
 SIAMESE_EXPORT int sgpu_h2d(void* deviceDst, const void* hostSrc, size_t bytes);
 /// Gather `count` device ranges into one host buffer (concatenated in order).
 /// Runs immediately; queued-but-unflushed codec work is left untouched.
+/// Exactly the sum of bytes[] is written; a range of 0 bytes moves nothing
+/// (its pointer is not read), and a call without a byte to move returns 0.
 SIAMESE_EXPORT int sgpu_gather(unsigned count, const void* const* deviceSrcs, const unsigned* bytes,
                                void* hostOut);
 
@@ -298,6 +300,10 @@ SIAMESE_EXPORT int sgpu_h2d_async(void* deviceDst, const void* hostSrc, size_t b
 /// host memory (sgpu_host_alloc) on the library's gather stream, without
 /// waiting for submissions still in flight.  Range i lands at offset
 /// sum over k < i of align16(bytes[k]) (16-byte aligned, one DMA for all).
+/// The bytes between a range's end and the next multiple of 16 are written
+/// as zero, and nothing is written at or past the sum of all align16(bytes[k]);
+/// a range of 0 bytes takes no room and moves nothing.  The device words read
+/// are the aligned 16-byte words that hold a byte of a range, whole.
 SIAMESE_EXPORT int sgpu_gather_completed(unsigned count, const void* const* deviceSrcs, const unsigned* bytes,
                                          void* pinnedOut);
 /// sgpu_gather_completed without waiting for the copy: returns a gather
@@ -305,7 +311,9 @@ SIAMESE_EXPORT int sgpu_gather_completed(unsigned count, const void* const* devi
 /// device work of any later submission runs (that work waits for them on the
 /// device), so the instances owning them may be driven on right away;
 /// pinnedOut holds the bytes once sgpu_gather_wait(ticket) returns 0.  May
-/// run beside instance calls, like sgpu_gather_completed.
+/// run beside instance calls, like sgpu_gather_completed.  Every call's
+/// ticket is larger than any earlier one; a call with count == 0, or whose ranges are all empty, moves
+/// nothing and still returns a ticket that sgpu_gather_wait takes.
 SIAMESE_EXPORT long long sgpu_gather_async(unsigned count, const void* const* deviceSrcs, const unsigned* bytes,
                                            void* pinnedOut);
 /// Wait until gather `ticket` and every earlier one have landed in host

@@ -3111,15 +3111,17 @@ int64_t Engine::gather_async_framed(unsigned count, const void* const* srcs, con
         return -1;
     std::lock_guard<std::mutex> lk(gatherMu_);
     const int64_t ticket = ++gNext_;
-    if (count == 0)
+    size_t total = 0;
+    for (unsigned i = 0; i < count; ++i)
+        total = align16(total + bytes[i] + (hdrLens ? hdrLens[i] : 0));
+    // (empty ranges only: nothing to move either, and a slot that has never
+    // held bytes has no staging area to name in a descriptor)
+    if (count == 0 || total == 0)
         return ticket;
     GatherSlot& g = gslots_[ticket % kGatherSlots];
     if (!gather_land(g))   // (the slot's previous gather, kGatherSlots back)
         return -1;
     const size_t upBytes = count * sizeof(IngestDesc);
-    size_t total = 0;
-    for (unsigned i = 0; i < count; ++i)
-        total = align16(total + bytes[i] + (hdrLens ? hdrLens[i] : 0));
     auto grow = [](uint8_t*& h, uint8_t*& d, size_t& cap, size_t need, bool host) {
         if (need <= cap)
             return;
@@ -3279,6 +3281,8 @@ bool Engine::gather(unsigned count, const void* const* srcs, const unsigned* byt
         descs[i].dst = total; // offset for now
         total = align16(total + bytes[i]);
     }
+    if (total == 0)   // (empty ranges only: no staging area may exist yet)
+        return true;
     const size_t upBytes = count * sizeof(IngestDesc);
     auto grow = [](uint8_t*& h, uint8_t*& d, size_t& cap, size_t need) {
         if (need <= cap)
